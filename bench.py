@@ -1,6 +1,11 @@
 """bench.py — images/sec forward+backward(+Adam) of the DeepLabV3+ MobileNetV2 path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, optionally writes the last timed step's outputs (--dump-outputs) and
+prints the result line (`value` img/s, `ms_per_step`).  Everything else it can measure — the fed leg, the gradient
+exchange on its own, the in-situ roofline blocks, the split-math leg, the other BASELINE.json configurations and the CPU
+baselines — runs only with --full (each still switched off by its --no-* option).
 
 N > 1 without a launcher: bench.py re-executes itself under `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU); started by torch.distributed.run it reads
@@ -12,7 +17,12 @@ synthetic and already in HBM when the timed region starts.  Workload = BASELINE.
 Deeplabv3(backbone='mobilenetv2', input_shape=(512,512,3), classes=21, OS=16), fp32, BatchNorm in training
 (batch-statistics) mode, dropout on.  `--head subpixel` = configs[2], `--backbone xception --os 8` = configs[3].
 
-`roofline` / `roofline_hbm` are measured IN SITU: after the timed region the same plan is launched eagerly on the same
+`--dump-outputs DIR` (after the timed steps, rank 0): loss.npy (float64), params.npy (the weights after the last Adam
+step), grads.npy (that step's gradients) and state.npy (BatchNorm moving statistics and other non-trained weights), float32;
+an array longer than DUMP_MAX_ELEMS is written as a fixed sample (seed 0, sorted indices), so the dump stays under 64 MB.
+Inputs and initial weights are seeded: the same arguments give the same inputs on every run and every build.
+
+With --full: `roofline` / `roofline_hbm` are measured IN SITU: after the timed region the same plan is launched eagerly on the same
 resident buffers with a HIP event between every two launches; each launch's algorithmic FLOPs / bytes (SURVEY §8d
 formulas, from its own arguments) are summed per kernel family and divided by the family's summed device time.
 `roofline` is the family with the largest share of the step (the fp32-MFMA 1x1-conv GEMMs), `roofline_hbm` the
@@ -64,10 +74,20 @@ def parse_args():
     ap.add_argument("--no-split-leg", action="store_true",
                     help="skip the second timed loop with DL3_GEMM_MATH=split (reported beside, never as, the headline)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the compact legs (configs[1] at B=2 / B=16, configs[2], configs[3]) of the default run")
+                    help="skip the fed leg and the compact legs (configs[1] at B=2 / B=16, configs[2], configs[3]) of a "
+                         "--full run")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = sweep thread counts up to os.cpu_count()")
-    ap.add_argument("--plan-json", default=None, help="write the per-launch in-situ table (op, shape, ms, FLOPs, bytes)")
-    return ap.parse_args()
+    ap.add_argument("--plan-json", default=None,
+                    help="with --full: write the per-launch in-situ table (op, shape, ms, FLOPs, bytes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, weights, gradients and BatchNorm state as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (fed leg, all-reduce alone, roofline, split math, other "
+                         "configurations, CPU baselines); a plain run times the headline only")
+    args = ap.parse_args()
+    if args.plan_json and not args.full:
+        ap.error("--plan-json is written by the in-situ roofline pass, which runs with --full only")
+    return args
 
 
 def respawn_under_launcher(args):
@@ -563,6 +583,23 @@ def compact_leg(args, **over):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 22   # per array: three float32 arrays of at most 16 MB keep the dump under 64 MB
+
+
+def dump_outputs(eng, loss, out_dir):
+    """--dump-outputs: what the last timed step left for its caller, one .npy per array (see the module docstring)"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": eng.params[:eng.n_param], "grads": eng.grads[:eng.n_param], "state": eng.state}
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], np.float64))
+    log("outputs of the last timed step written to %s" % out_dir)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -645,9 +682,11 @@ def main():
     dt = dp.max_over_ranks(time.perf_counter() - t0)
     loss = eng.loss_value()
     log("timed %d steps: %.1f ms/step" % (args.steps, 1e3 * dt / args.steps))
-    ar_ms = allreduce_ms()
+    if args.dump_outputs and dp.rank == 0:
+        dump_outputs(eng, loss, args.dump_outputs)   # before any side leg steps the engine again
+    ar_ms = allreduce_ms() if args.full else None
     fed = None
-    if not args.no_legs and (dp.world > 1 or not eng.external_nnz):
+    if args.full and not args.no_legs and (dp.world > 1 or not eng.external_nnz):
         # (N > 1: every rank feeds its own shard into the data-parallel step; N = 1: the plain resident step)
         try:
             fed = fed_run(eng, args.steps, step=step if dp.world > 1 else None, dp=dp if dp.world > 1 else None)
@@ -687,7 +726,7 @@ def main():
             rec["allreduce_ms"] = ar_ms  # one exchange of the %d-float arena on its own, max over ranks (part of ms_per_step)
         if fed is not None:
             rec["fed"] = fed   # the same steps fed from pinned host memory (never `value`: that is the resident rate)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             rows = insitu_profile(eng)
             log("in-situ profile done: %.2f ms for %d launches" % (sum(r["ms"] for r in rows), len(rows)))
             rec.update(roofline_blocks(rows, args))
@@ -697,11 +736,11 @@ def main():
                                "size": args.size, "rows": rows}, f, indent=0)
         rec["config"]["deferred_fold_workspaces_mb"] = round(eng.own_fold_ws_bytes / 2 ** 20, 1)
         default_run = default_cfg and args.batch == 128 and args.bn_mode == "batch"
-        if dp.world == 1 and not args.no_split_leg and rec["config"]["matrix_math"] == "f32":
+        if args.full and dp.world == 1 and not args.no_split_leg and rec["config"]["matrix_math"] == "f32":
             del step
             eng = model = None
             rec["split_math"] = split_math_leg(args)
-        if dp.world == 1 and default_run and not args.no_legs:
+        if args.full and dp.world == 1 and default_run and not args.no_legs:
             # what else BASELINE.json lists, timed by the same run: the reference's own batch sizes for
             # configs[1] (notebook: 2, SegModel default: 16, utils.py:162), configs[2] (Subpixel head) and configs[3]
             # (Xception OS=8).  `value` above is untouched by these.
@@ -716,7 +755,7 @@ def main():
                 "cfg4_xception_os8_b16": compact_leg(args, backbone="xception", os=8, batch=16),
             }
             _free_engines()
-        if dp.world == 1 and not args.no_cpu_baseline:
+        if args.full and dp.world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline_leg(args)
             log("cpu baseline done")
         print(json.dumps(rec), flush=True)

@@ -220,7 +220,7 @@ def test_bench_self_spawns_its_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "2",
-           "--size", "128", "--no-cpu-baseline", "--no-roofline"]
+           "--size", "128", "--full", "--no-cpu-baseline", "--no-roofline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -239,6 +239,40 @@ def test_bench_self_spawns_its_ranks():
     env2 = dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     res = subprocess.run(cmd, env=env2, capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "WORLD_SIZE" in res.stderr
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W` times the headline only (the side measurements run with
+    --full), and --dump-outputs writes what the last timed step left: loss, weights after Adam, gradients, BatchNorm state —
+    float, finite, under 64 MB, and the same on a second run with the same arguments (seeded inputs and weights)."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    full_only = ("fed", "allreduce_ms", "insitu_step_ms", "roofline", "roofline_hbm", "split_math", "by_batch", "configs",
+                 "cpu_baseline")
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("run%d" % run))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2",
+               "--size", "128", "--dump-outputs", d]
+        res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["unit"] == "img/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert abs(rec["value"] - 2 * 3 / (rec["ms_per_step"] * 3e-3)) < 1e-6 * rec["value"]
+        assert [k for k in full_only if k in rec] == []
+        files = sorted(os.listdir(d))
+        assert files == ["grads.npy", "loss.npy", "params.npy", "state.npy"]
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        out = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+        assert out["loss"][0] == rec["config"]["final_loss"] and np.abs(out["grads"]).max() > 0
+        dumps.append(out)
+    for k, a in dumps[0].items():
+        b = dumps[1][k]
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-6 * np.abs(a).max(), k
 
 
 def test_data_parallel_step_with_a_one_rank_rccl_communicator_under_hipgraph():

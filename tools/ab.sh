@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-call A/B of environment / library variants on one bench configuration (GPU box):
 #   bash tools/r4/ab.sh OUTDIR "bench args" "NAME|ENV=V ENV2=V ..." ...
-# every variant runs `python bench.py <bench args> --no-cpu-baseline --no-split-leg --no-legs --plan-json OUT/NAME.plan.json`
+# every variant runs `python bench.py <bench args> --full --no-cpu-baseline --no-split-leg --no-legs --plan-json OUT/NAME.plan.json`
 # and leaves OUT/NAME.json; a summary table (img/s, ms/step, per-direction GEMM milliseconds from the in-situ plan) is printed
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 out=$REPO/gpurun_out/$1; shift
@@ -10,7 +10,7 @@ mkdir -p $out
 cd $REPO
 for spec in "$@"; do
   name=${spec%%|*}; envs=${spec#*|}
-  env $envs timeout 900 python bench.py $bargs --no-cpu-baseline --no-split-leg --no-legs --plan-json $out/$name.plan.json \
+  env $envs timeout 900 python bench.py $bargs --full --no-cpu-baseline --no-split-leg --no-legs --plan-json $out/$name.plan.json \
       > $out/$name.json 2> $out/$name.err
 done
 python - "$out" <<'PY'

@@ -8,12 +8,12 @@ export TMPDIR=/tmp
 cd $REPO
 # 0. the whole -m gpu suite, as the driver runs it
 timeout 2400 python -m pytest tests -m gpu -q --durations=12 > $out/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $out/pytest_gpu.log; tail -3 $out/pytest_gpu.log
-# 1. the driver's own command (all legs)
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+# 1. the driver's command with every side measurement (--full)
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc $?" >> $out/smoke.log; tail -2 $out/smoke.log
 # 2. bench lines of the other configurations (no CPU legs)
 L=$out/bench_lines.jsonl; : > $L
-B="python bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+B="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"
 for b in 2 4 8 16 32 64; do $B --no-split-leg --no-roofline --no-legs --batch $b 2>/dev/null | tail -1 >> $L; done
 $B --head subpixel --plan-json $out/plan_cfg3_subpixel.json 2>/dev/null | tail -1 >> $L
 $B --head original --no-split-leg 2>/dev/null | tail -1 >> $L
@@ -22,7 +22,7 @@ $B --backbone xception --os 8 --batch 32 --steps 10 2>/dev/null | tail -1 >> $L
 $B --backbone xception --os 16 --batch 16 --steps 10 --no-split-leg --no-roofline 2>/dev/null | tail -1 >> $L
 # 3. rocprofv3 kernel stats of the same commands
 cd /tmp
-prof() { tag=$1; shift; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o bench -- python $REPO/bench.py --no-cpu-baseline --no-split-leg --no-legs --steps 10 --warmup 3 --plan-json $out/plan_$tag.json "$@" > $out/prof_$tag.log 2>&1; }
+prof() { tag=$1; shift; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o bench -- python $REPO/bench.py --full --no-cpu-baseline --no-split-leg --no-legs --steps 10 --warmup 3 --plan-json $out/plan_$tag.json "$@" > $out/prof_$tag.log 2>&1; }
 prof cfg2_b128
 prof cfg2_b16 --batch 16
 prof cfg2_b2 --batch 2 --steps 20

@@ -110,7 +110,8 @@ int dl3_pwconv_fwd_impl(int M, int K, int N);
 /* ... and the route of a launch by name, for plans that want to assert what they benchmark (tests/test_host.py):
  * dir 0 = forward (as dl3_pwconv_fwd_impl), 1 = bwd-data with the single-tensor dY, a mask operand and no addend, 2 = the
  * weight gradient (two-tensor operand), 3 = bwd-data with the single-tensor dY (rows back to back) and neither mask, addend
- * nor BatchNorm sums, 4 = the weight gradient with a single-tensor dY and a bias gradient (3, 4: the logits layer).
+ * nor BatchNorm sums (the logits layer), 4 = the weight gradient with a single-tensor dY, folded by the launch (dw given),
+ * bias gradient optional (2, 4: 16-byte aligned operands, leading dimensions multiples of 4).
  * Returns DL3_ROUTE_*.  Diagnostic only. */
 #define DL3_ROUTE_TILED 0      /* pw_gemm_stream_kernel / pw_gemm_kernel / pw_wgrad_kernel */
 #define DL3_ROUTE_WS_HBM 1     /* pw_fwd_ws_kernel */

@@ -2332,8 +2332,8 @@ __global__ __launch_bounds__(64 * NW) void pw_wgrad_narrow_kernel(WgradArgs P, f
       gsum += gv;
 #pragma unroll
       for (int h = 0; h < HB; h++) {
-        f32x4 v = xr[sl][ks][h];
-        if (xform) v = dl3_act4(ld4(cfx + 128 * h + 4 * l31) * v + ld4(cfx + K + 128 * h + 4 * l31), P.x_act);
+        // (scale 1, shift 0 without a BatchNorm: an activation-only view is still rectified)
+        const f32x4 v = dl3_act4(ld4(cfx + 128 * h + 4 * l31) * xr[sl][ks][h] + ld4(cfx + K + 128 * h + 4 * l31), P.x_act);
 #pragma unroll
         for (int e = 0; e < 4; e++) acc[4 * h + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[e], gv, acc[4 * h + e], 0, 0, 0);
       }
@@ -3161,7 +3161,10 @@ static bool wgrad_row_ok(const WgCfg &c, int M, int K, int N) {
 extern "C" int dl3_pwconv_route(int dir, int M, int K, int N) {
   if (M <= 0 || K <= 0 || N <= 0 || split_math()) return DL3_ROUTE_TILED;
   if (dir == 2) return wgrad_row_ok(pick_wgrad(M, K, N, true), M, K, N) ? DL3_ROUTE_WGRAD_ROW : DL3_ROUTE_TILED;
-  if (dir == 4) return wgrad_narrow_shape(M, K, N) ? DL3_ROUTE_NARROW : DL3_ROUTE_TILED;
+  if (dir == 4) {   // (single-tensor dY, dw given: the launch folds its own slabs)
+    if (wgrad_narrow_shape(M, K, N)) return DL3_ROUTE_NARROW;
+    return wgrad_row_ok(pick_wgrad(M, K, N, false), M, K, N) ? DL3_ROUTE_WGRAD_ROW : DL3_ROUTE_TILED;
+  }
   GemmArgs A{};
   if (dir == 3) {   // bwd-data of a layer K -> N without a mask operand: reduces over N, K wide
     A.M = M; A.K = N; A.N = K; A.ldc = K; A.lda = N;

@@ -725,6 +725,53 @@ def test_subpixel_with_kernel_size_above_one(k, padding):
         assert e < 2e-4, (n, e)
 
 
+def test_activation_without_batchnorm_into_the_logits_layer():
+    """Input -> Conv2D(256, 1) -> Activation("relu") -> Conv2D(21, 1) -> softmax at B = 2 (131 072 rows): the logits
+    convolution reads a view with an activation and no BatchNorm (scale and shift NULL), and its weight gradient takes
+    pw_wgrad_narrow_kernel (tests/test_host.py asserts the plan), which used to rectify x only when a scale came with the
+    activation — the graph trained on the gradient of the unrectified input.  Logits, loss and every gradient against a
+    float64 torch-autograd restatement written here."""
+    import dl3_amd  # noqa: F401
+    from dl3_amd import graph as G
+    from tests.test_host import _act_only_logits_model
+    H, W, cin, classes, B = 256, 256, 8, 21, 2
+    model = _act_only_logits_model(G, H, W, cin, classes)
+    rng = np.random.default_rng(12)
+    for l in model.layers:
+        if l.weights:
+            k, b = l.get_weights()
+            l.set_weights([rng.normal(0, 1.0 / np.sqrt(k.shape[2]), k.shape).astype(np.float32),
+                           rng.normal(0, 0.5, b.shape).astype(np.float32)])
+    xin = rng.normal(0, 1, (B, H, W, cin)).astype(np.float32)
+    labels = rng.integers(0, classes + 1, (B, H * W)).astype(np.float32)
+    sw = ((labels < classes) * rng.uniform(0.5, 2.0, labels.shape)).astype(np.float32)
+    eng = model._engine(B, True, dropout=False, use_graph=False)
+    eng.set_input(xin)
+    eng.set_targets(labels, sw)
+    eng.fwd_bwd()
+    torch.cuda.synchronize()
+    # ---- float64 restatement
+    P = {n: torch.tensor(np.asarray(w, np.float64), requires_grad=True) for l in model.layers for n, w in l.weights.items()}
+    xt = torch.tensor(xin.astype(np.float64)).reshape(B * H * W, cin)
+    a = torch.relu(xt @ P["c0/kernel:0"].reshape(cin, 256) + P["c0/bias:0"])
+    logits = (a @ P["logits/kernel:0"].reshape(256, classes) + P["logits/bias:0"]).reshape(B, H * W, classes)
+    t = torch.tensor(labels.astype(np.int64))
+    w = torch.tensor(sw.astype(np.float64))
+    p = torch.softmax(logits, -1)
+    pt = torch.gather(p, 2, t.clamp(max=classes - 1).unsqueeze(-1)).squeeze(-1).clamp(1e-7, 1 - 1e-7)
+    ell = torch.where(t < classes, -torch.log(pt), torch.zeros_like(pt))
+    loss = (ell * w).sum() / (w != 0).sum()
+    loss.backward()
+    got = eng.logits().reshape(B, H * W, classes)
+    assert _l2(got, logits.detach().numpy()) < 2e-4
+    assert abs(float(eng.loss[0].item()) - float(loss)) < 1e-5 * abs(float(loss))
+    assert sorted(P) == ["c0/bias:0", "c0/kernel:0", "logits/bias:0", "logits/kernel:0"]
+    for n, pt_ in P.items():
+        e = _l2(eng.grad_of(n), pt_.grad.numpy())
+        print("   %-16s grad rel-L2 %.2e" % (n, e))
+        assert e < 2e-4, (n, e)
+
+
 def test_compile_accepts_the_references_adam_object():
     """segmentation.ipynb cell 2: compile(optimizer=Adam(lr=7e-4, epsilon=1e-8, decay=1e-6), ...) — the object and the
     equivalent dict must train identically (bit for bit: same launches, same scalars)."""

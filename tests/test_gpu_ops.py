@@ -19,12 +19,39 @@ def L():
     return capi.lib()
 
 
-def _xform(rng, C, act):
-    if act is None:
+FORMS = ("none", "affine", "act", "affine+act")   # the input transforms a view can carry (engine.View.xform)
+ACT_NAME = {1: "relu", 2: "relu6"}
+
+
+def _xform(rng, C, act, form=None):
+    """(in_scale, in_shift, in_act) of an input view.  form None: no transform when act is None, else affine + act (the
+    cases written before the forms); "none", "affine" (BatchNorm without activation), "act" (no BatchNorm: scale and shift
+    NULL) or "affine+act"."""
+    if form is None:
+        form = "none" if act is None else "affine+act"
+    if form == "none":
         return None, None, 0
+    if form == "act":
+        return None, None, act
     s = rng.uniform(0.5, 1.5, C).astype(np.float32)
     t = rng.normal(0, 0.5, C).astype(np.float32)
-    return s, t, act
+    return s, t, (act if form == "affine+act" else 0)
+
+
+def _z(x, s, t):
+    """the pre-activation input of a view, float64"""
+    x = np.asarray(x, np.float64)
+    return x if s is None else s * x + t
+
+
+def _form_cases(routes, acts=(1, 2)):
+    """pytest params: every (route, case) under the four transform forms, the forms with an activation once per act"""
+    out = []
+    for name, case in routes:
+        for form in FORMS:
+            for a in (acts if form.endswith("act") else (None,)):
+                out.append(pytest.param(case, form, a, id="%s-%s%s" % (name, form, "-" + ACT_NAME[a] if a else "")))
+    return out
 
 
 DW_CASES = [
@@ -73,13 +100,14 @@ def _dw_geom(H, W, stride, rate, pads):
 
 @pytest.mark.parametrize("case", DW_CASES)
 def test_dwconv_fwd(L, case):
-    N, H, W, C, stride, rate, pads, impl, act = case
+    N, H, W, C, stride, rate, pads, impl, act = case[:9]
+    form = case[9] if len(case) > 9 else None
     rng = np.random.default_rng(0)
     Ho, Wo, pt, pl = _dw_geom(H, W, stride, rate, pads)
     x = rng.normal(0, 1, (N, H, W, C)).astype(np.float32)
     w = rng.normal(0, 0.3, (3, 3, C)).astype(np.float32)
-    s, t, a = _xform(rng, C, act)
-    xin = x if s is None else np_act(s * x + t, a)
+    s, t, a = _xform(rng, C, act, form)
+    xin = np_act(_z(x, s, t), a)
     ref = O.depthwise3x3(xin.astype(np.float64), w.astype(np.float64), stride, rate, pt, pl, Ho, Wo)
     P = L.dl3_dwconv3x3_partials(N, H, W, C, stride, rate, Ho, Wo, impl)
     y, part = empty(N, Ho, Wo, C), empty(P, C, 2)
@@ -94,7 +122,8 @@ def test_dwconv_fwd(L, case):
 
 @pytest.mark.parametrize("case", DW_CASES)
 def test_dwconv_bwd(L, case):
-    N, H, W, C, stride, rate, pads, impl, act = case
+    N, H, W, C, stride, rate, pads, impl, act = case[:9]
+    form = case[9] if len(case) > 9 else None
     rng = np.random.default_rng(1)
     Ho, Wo, pt, pl = _dw_geom(H, W, stride, rate, pads)
     x = rng.normal(0, 1, (N, H, W, C)).astype(np.float32)
@@ -105,8 +134,8 @@ def test_dwconv_bwd(L, case):
     add = rng.normal(0, 1, (N, H, W, C)).astype(np.float32)
     mean = rng.normal(0, 1, C).astype(np.float32)
     invstd = rng.uniform(0.5, 2, C).astype(np.float32)
-    s, t, a = _xform(rng, C, act)
-    z = x.astype(np.float64) if s is None else (s * x.astype(np.float64) + t)
+    s, t, a = _xform(rng, C, act, form)
+    z = _z(x, s, t)
     xin = np_act(z, a)
     dY = cA * g.astype(np.float64) + cB * yraw + cC
     tape = O.Tape()
@@ -243,16 +272,16 @@ PW_CASES = [
 
 @pytest.mark.parametrize("case", PW_CASES)
 def test_pwconv_fwd(L, case):
-    M, K, N, lxe, lye, bias, act = case
+    M, K, N, lxe, lye, bias, act = case[:7]
+    form = case[7] if len(case) > 7 else None
     rng = np.random.default_rng(3)
     ldx, ldy = K + lxe, N + lye
     xfull = rng.normal(0, 1, (M, ldx)).astype(np.float32)
     w = rng.normal(0, 0.2, (K, N)).astype(np.float32)
     b = rng.normal(0, 1, N).astype(np.float32) if bias else None
-    s, t, a = _xform(rng, K, act)
+    s, t, a = _xform(rng, K, act, form)
     xoff = lxe
-    x = xfull[:, xoff:xoff + K].astype(np.float64)
-    xin = x if s is None else np_act(s * x + t, a)
+    xin = np_act(_z(xfull[:, xoff:xoff + K], s, t), a)
     ref = xin @ w.astype(np.float64) + (b if bias else 0)
     P = L.dl3_pwconv_partials(M, K, N)
     yfull = torch.zeros(M, ldy, dtype=torch.float32, device="cuda")
@@ -380,22 +409,36 @@ BD_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", BD_CASES)
-def test_pwconv_bwd_data(L, case):
-    M, K, N, act, two, addmode, stats = case
+def _place(a, off=0, extra=0):
+    """a [M, C] operand at column `off` of a wider [M, off + C + extra] device buffer whose other columns hold a large
+    finite value (a kernel that reads them gets a wrong result, one that loads and discards them does not): (buffer, ld)"""
+    if not off and not extra:
+        return dev(a), a.shape[1]
+    M, C = a.shape
+    full = np.full((M, off + C + extra), 1e4, np.float32)
+    full[:, off:off + C] = a
+    return dev(full), off + C + extra
+
+
+def _bwd_data(L, M, K, N, act, two, addmode, stats, form=None, lay=None):
+    """dl3_pwconv_bwd_data against float64.  lay: {operand: (column offset, extra leading-dimension width)} for "x", "g"
+    (yraw shares its layout) and "dx" (the addend shares it; dx lands in a NaN-filled buffer whose other columns must stay
+    NaN) — the strided operands the engine passes (views into concat buffers)"""
+    lay = lay or {}
+    (xo, xe), (go, ge), (do, de) = lay.get("x", (0, 0)), lay.get("g", (0, 0)), lay.get("dx", (0, 0))
     rng = np.random.default_rng(4)
     g = rng.normal(0, 1, (M, N)).astype(np.float32)
     yraw = rng.normal(0, 1, (M, N)).astype(np.float32)
     cA, cB, cC = [rng.normal(0, 1, N).astype(np.float32) for _ in range(3)]
     w = rng.normal(0, 0.2, (K, N)).astype(np.float32)
     x = rng.normal(0, 1, (M, K)).astype(np.float32)
-    s, t, a = _xform(rng, K, act)
+    s, t, a = _xform(rng, K, act, form)
     mean = rng.normal(0, 1, K).astype(np.float32)
     invstd = rng.uniform(0.5, 2, K).astype(np.float32)
     dY = (cA * g.astype(np.float64) + cB * yraw + cC) if two else g.astype(np.float64)
     ref = dY @ w.astype(np.float64).T
-    if s is not None:
-        ref = ref * np_mask(s * x.astype(np.float64) + t, a)
+    if a:
+        ref = ref * np_mask(_z(x, s, t), a)
     add_div, add_scale, add = 1, 1.0, None
     if addmode == 1:
         add = rng.normal(0, 1, (M, K)).astype(np.float32)
@@ -408,18 +451,36 @@ def test_pwconv_bwd_data(L, case):
     call("dl3_transpose", ptr(dev(w)), ptr(wT), K, N)
     assert np.array_equal(host(wT), w.T)
     P = L.dl3_pwconv_partials(M, N, K)
-    dx, dpart = empty(M, K), empty(P, K, 2)
-    need_x = s is not None or stats
-    call("dl3_pwconv_bwd_data", ptr(dev(g)), N, ptr(dev(yraw)) if two else None, N, ptr(dev(cA)) if two else None,
-         ptr(dev(cB)) if two else None, ptr(dev(cC)) if two else None, ptr(wT), ptr(dx), K,
-         ptr(dev(x)) if need_x else None, K, ptr(dev(s)) if s is not None else None,
-         ptr(dev(t)) if t is not None else None, a, ptr(dev(add)) if add is not None else None, K, add_div, add_scale,
+    lddx = do + K + de
+    dxb, dpart = empty(M, lddx), empty(P, K, 2)
+    need_x = a != 0 or stats
+    gd, ldg = _place(g, go, ge)
+    yd, _ = _place(yraw, go, ge) if two else (None, 0)
+    xd, ldx = _place(x, xo, xe) if need_x else (None, K)
+    ldadd = K
+    if add is not None and addmode == 1:
+        addd, ldadd = _place(add, do, de)
+        addp = ptr(addd, do)
+    else:
+        addp = ptr(dev(add)) if add is not None else None
+    call("dl3_pwconv_bwd_data", ptr(gd, go), ldg, ptr(yd, go) if two else None, ldg, ptr(dev(cA)) if two else None,
+         ptr(dev(cB)) if two else None, ptr(dev(cC)) if two else None, ptr(wT), ptr(dxb, do), lddx,
+         ptr(xd, xo) if need_x else None, ldx, ptr(dev(s)) if s is not None else None,
+         ptr(dev(t)) if t is not None else None, a, addp, ldadd, add_div, add_scale,
          ptr(dev(mean)) if stats else None, ptr(dev(invstd)) if stats else None, ptr(dpart) if stats else None, M, K, N)
-    assert relerr(host(dx), ref) < TOL
+    dxh = host(dxb)
+    assert relerr(dxh[:, do:do + K], ref) < TOL
+    if do or de:
+        assert np.isnan(dxh[:, :do]).all() and np.isnan(dxh[:, do + K:]).all()   # nothing written outside the slice
     if stats:
         s1, s2 = fold_partials(dpart, P, K)
         assert relerr(s1, ref.sum(0)) < 1e-3
         assert relerr(s2, (ref * (x - mean) * invstd).sum(0)) < 1e-3
+
+
+@pytest.mark.parametrize("case", BD_CASES)
+def test_pwconv_bwd_data(L, case):
+    _bwd_data(L, *case)
 
 
 MSK_CASES = [
@@ -464,40 +525,54 @@ BW_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", BW_CASES)
-def test_pwconv_bwd_weight(L, case):
-    M, K, N, act, two, dbias = case
+def _bwd_weight(L, M, K, N, act, two, dbias, form=None, lay=None):
+    """dl3_pwconv_bwd_weight against float64 (the reference summed in row chunks).  lay: {operand: (column offset, extra
+    leading-dimension width)} for "x" and "g" (yraw shares its layout)"""
+    lay = lay or {}
+    (xo, xe), (go, ge) = lay.get("x", (0, 0)), lay.get("g", (0, 0))
     rng = np.random.default_rng(5)
     g = rng.normal(0, 1, (M, N)).astype(np.float32)
     yraw = rng.normal(0, 1, (M, N)).astype(np.float32)
     cA, cB, cC = [rng.normal(0, 1, N).astype(np.float32) for _ in range(3)]
     x = rng.normal(0, 1, (M, K)).astype(np.float32)
-    s, t, a = _xform(rng, K, act)
-    xin = x.astype(np.float64) if s is None else np_act(s * x.astype(np.float64) + t, a)
-    dY = (cA * g.astype(np.float64) + cB * yraw + cC) if two else g.astype(np.float64)
-    ref = xin.T @ dY
+    s, t, a = _xform(rng, K, act, form)
+    ref, db_ref = np.zeros((K, N)), np.zeros(N)
+    for m0 in range(0, M, 1 << 16):
+        sl = slice(m0, m0 + (1 << 16))
+        dY = (cA * g[sl].astype(np.float64) + cB * yraw[sl] + cC) if two else g[sl].astype(np.float64)
+        ref += np_act(_z(x[sl], s, t), a).T @ dY
+        db_ref += dY.sum(0)
     nbytes = L.dl3_pwconv_bwd_weight_workspace(M, K, N)
     ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device="cuda")
     dw, db = empty(K, N), empty(N)
-    call("dl3_pwconv_bwd_weight", ptr(dev(x)), K, ptr(dev(s)) if s is not None else None,
-         ptr(dev(t)) if t is not None else None, a, ptr(dev(g)), N, ptr(dev(yraw)) if two else None, N,
+    xd, ldx = _place(x, xo, xe)
+    gd, ldg = _place(g, go, ge)
+    yd, _ = _place(yraw, go, ge) if two else (None, 0)
+    call("dl3_pwconv_bwd_weight", ptr(xd, xo), ldx, ptr(dev(s)) if s is not None else None,
+         ptr(dev(t)) if t is not None else None, a, ptr(gd, go), ldg, ptr(yd, go) if two else None, ldg,
          ptr(dev(cA)) if two else None, ptr(dev(cB)) if two else None, ptr(dev(cC)) if two else None, ptr(dw),
          ptr(db) if dbias else None, M, K, N, ptr(ws), nbytes)
     assert relerr(host(dw), ref) < TOL
     if dbias:
-        assert relerr(host(db), dY.sum(0)) < TOL
+        assert relerr(host(db), db_ref) < TOL
+
+
+@pytest.mark.parametrize("case", BW_CASES)
+def test_pwconv_bwd_weight(L, case):
+    _bwd_weight(L, *case)
 
 
 @pytest.mark.parametrize("case", [c for c in BW_CASES if c[4] and not c[5]] + [(130, 24, 144, 2, True, False)])
 def test_pwconv_bwd_weight_writes_dy(L, case):
     """dl3_pwconv_bwd_weight_dy: the same weight gradient bit for bit, plus dY = cA*g + cB*y + cC written once"""
-    M, K, N, act, two, dbias = case
+    M, K, N, act, two, dbias = case[:6]
+    form = case[6] if len(case) > 6 else None
     rng = np.random.default_rng(15)
     g = rng.normal(0, 1, (M, N)).astype(np.float32)
     yraw = rng.normal(0, 1, (M, N)).astype(np.float32)
     cA, cB, cC = [rng.normal(0, 1, N).astype(np.float32) for _ in range(3)]
     x = rng.normal(0, 1, (M, K)).astype(np.float32)
-    s, t, a = _xform(rng, K, act)
+    s, t, a = _xform(rng, K, act, form)
     nbytes = L.dl3_pwconv_bwd_weight_workspace(M, K, N)
     ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device="cuda")
     args = (ptr(dev(x)), K, ptr(dev(s)) if s is not None else None, ptr(dev(t)) if t is not None else None, a,
@@ -513,6 +588,8 @@ def test_pwconv_bwd_weight_writes_dy(L, case):
     ref = cA.astype(np.float64) * g + cB.astype(np.float64) * yraw + cC
     assert relerr(got[:, :N], ref) < 1e-6
     assert np.isnan(got[:, N:]).all()   # nothing written beyond the N columns
+    if form is not None:   # ... and the weight gradient itself against float64
+        assert relerr(host(dw1), np_act(_z(x, s, t), a).T @ ref) < TOL
 
 
 @pytest.mark.parametrize("cfg", range(10))
@@ -541,7 +618,7 @@ def test_pwconv_bwd_weight_dy_benchmark_routes(L, case):
 def test_pwconv_bwd_weight_one_tile_row(L, case):
     """round 6 (pw_wgrad_row_kernel): K fits one tile row — plain dY (no BatchNorm behind the convolution) and the two-tensor
     operand, without the dY store; N ragged against the 128-wide tiles (idle waves), M not a multiple of the 16-row stage"""
-    assert L.dl3_pwconv_route(2, case[0], case[1], case[2]) == 4
+    assert L.dl3_pwconv_route(2 if case[4] else 4, case[0], case[1], case[2]) == 4
     test_pwconv_bwd_weight(L, case)
 
 
@@ -666,7 +743,8 @@ FUSED_CASES = [
 def test_pwconv_bwd_fused(L, case):
     """dl3_pwconv_bwd_fused == dl3_pwconv_bwd_weight + dl3_pwconv_bwd_data of the same layer (float64 reference): weight
     gradient (slabs folded by the op or left for the caller), masked data gradient + addend, BatchNorm-backward sums"""
-    M, K, N, act, two, has_add, stats = case
+    M, K, N, act, two, has_add, stats = case[:7]
+    form = case[7] if len(case) > 7 else None
     assert L.dl3_pwconv_bwd_fused_supported(M, K, N) == (2 if K <= 64 else 1)
     rng = np.random.default_rng(16)
     g = rng.normal(0, 1, (M, N)).astype(np.float32)
@@ -675,11 +753,11 @@ def test_pwconv_bwd_fused(L, case):
     w = rng.normal(0, 0.2, (K, N)).astype(np.float32)
     x = rng.normal(0, 1, (M, K)).astype(np.float32)
     other = rng.normal(0, 1, (M, K)).astype(np.float32)
-    s, t, a = _xform(rng, K, act)
+    s, t, a = _xform(rng, K, act, form)
     mean = rng.normal(0, 1, K).astype(np.float32)
     invstd = rng.uniform(0.5, 2, K).astype(np.float32)
     add = rng.normal(0, 1, (M, K)).astype(np.float32) if has_add else None
-    z = x.astype(np.float64) if s is None else (s * x.astype(np.float64) + t)
+    z = _z(x, s, t)
     dY = (cA * g.astype(np.float64) + cB * yraw + cC) if two else g.astype(np.float64)
     dw_ref = np_act(z, a).T @ dY
     dx_ref = dY @ w.astype(np.float64).T * np_mask(z, a)
@@ -737,14 +815,14 @@ WS_CASES = [
 ]
 
 
-def _pw_fwd_chunked(L, M, K, N, lxe, lye, bias, act, stats, seed=21, chunk=1 << 16):
+def _pw_fwd_chunked(L, M, K, N, lxe, lye, bias, act, stats, seed=21, chunk=1 << 16, form=None):
     """dl3_pwconv_fwd against float64, the reference evaluated chunk by chunk (M up to millions of rows)"""
     rng = np.random.default_rng(seed)
     ldx, ldy = K + lxe, N + lye
     xfull = rng.normal(0, 1, (M, ldx)).astype(np.float32)
     w = rng.normal(0, 0.2, (K, N)).astype(np.float32)
     b = rng.normal(0, 1, N).astype(np.float32) if bias else None
-    s, t, a = _xform(rng, K, act)
+    s, t, a = _xform(rng, K, act, form)
     P = L.dl3_pwconv_partials(M, K, N)
     yfull = torch.zeros(M, ldy, dtype=torch.float32, device="cuda")
     part = empty(P, N, 2) if stats else None
@@ -756,8 +834,7 @@ def _pw_fwd_chunked(L, M, K, N, lxe, lye, bias, act, stats, seed=21, chunk=1 << 
     w64 = w.astype(np.float64)
     s1r, s2r, worst, scale = np.zeros(N), np.zeros(N), 0.0, 0.0
     for m0 in range(0, M, chunk):
-        x = xfull[m0:m0 + chunk, lxe:lxe + K].astype(np.float64)
-        xin = x if s is None else np_act(s * x + t, a)
+        xin = np_act(_z(xfull[m0:m0 + chunk, lxe:lxe + K], s, t), a)
         ref = xin @ w64 + (b if bias else 0)
         worst = max(worst, float(np.abs(y[m0:m0 + chunk, lye:] - ref).max()))
         scale = max(scale, float(np.abs(ref).max()))
@@ -1606,3 +1683,270 @@ def test_seg_counts_and_metrics_bit_exact(L, B, HW, C):
     assert U.Jaccard_from_counts(got) == U.Jaccard(yt[:, :, None], probs)
     assert U.accuracy_from_counts(got) == U.sparse_accuracy_ignoring_last_label(yt[:, :, None], probs)
     assert U.Jaccard_from_counts(got) == O.jaccard(yt, probs)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# every 1x1-convolution route under the four input transforms a view can carry (engine.View.xform: none, BatchNorm
+# without activation, activation without BatchNorm — scale and shift NULL —, BatchNorm + activation), and the backward
+# ops on the strided / misaligned operands the engine hands them.  Each case asserts its route where a diagnostic exists
+# (dl3_pwconv_route), so that a threshold change fails the case instead of moving it to another kernel unseen.
+R_TILED, R_WS_HBM, R_WS_MFMA, R_KSPLIT, R_ROW, R_NARROW = range(6)
+
+FWD_FORM_ROUTES = [
+    # name, (M, K, N, ldx_extra, ldy_extra, bias, stats, chunked), route
+    ("stream", (1000, 160, 960, 0, 0, False, True, False), R_TILED),
+    ("ws_hbm", (32768 + 77, 16, 96, 0, 0, False, True, True), R_WS_HBM),
+    ("ws2", (98304 + 7, 96, 192, 0, 0, True, True, True), R_WS_MFMA),
+    ("logits_packed", (32768 + 13, 256, 21, 0, 0, True, True, True), R_NARROW),
+    ("ksplit32", (2048, 960, 160, 0, 0, False, True, False), R_KSPLIT),
+    ("colsplit", (32768 + 64, 256, 608, 0, 0, True, True, True), None),
+]
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([(n, (c, r)) for n, c, r in FWD_FORM_ROUTES]))
+def test_pwconv_fwd_transform_forms(L, case, form, act):
+    """dl3_pwconv_fwd on each forward route (pw_gemm_stream_kernel, pw_fwd_ws_kernel, pw_ws2_kernel, its packed-logits
+    FLAT form, pw_ksplit32_kernel, and the column split — two launches, no diagnostic) under each input transform"""
+    (M, K, N, lxe, lye, bias, stats, chunked), route = case
+    if route is not None:
+        assert L.dl3_pwconv_route(0, M, K, N) == route
+    else:
+        assert L.dl3_pwconv_route(0, M, K, N) == R_TILED and N % 128 == 96 and M >= 32768   # the column split's shape
+    if chunked:
+        _pw_fwd_chunked(L, M, K, N, lxe, lye, bias, act, stats, form=form)
+        release()
+    else:
+        test_pwconv_fwd(L, (M, K, N, lxe, lye, bias, act, form))
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([("rows_f64", (3, 320, 256, 8, 4))]))
+def test_pwconv_fwd_rows_transform_forms(L, case, form, act):
+    """dl3_pwconv_fwd_rows (pw_rows_f64_kernel) under each input transform: the float64 product of the float32-transformed
+    input, rounded once"""
+    M, K, N, lxe, lye = case
+    rng = np.random.default_rng(41)
+    ldx, ldy = K + lxe, N + lye
+    xf = rng.normal(0, 1, (M, ldx)).astype(np.float32)
+    w = rng.normal(0, 0.2, (K, N)).astype(np.float32)
+    bias = rng.normal(0, 0.5, N).astype(np.float32)
+    s, t, a = _xform(rng, K, act, form)
+    x = xf[:, lxe:]
+    t32 = np_act(x if s is None else x * s + t, a)                  # the transform itself is float32 arithmetic
+    ref = t32.astype(np.float64) @ w.astype(np.float64) + bias
+    yfull = torch.zeros(M, ldy, dtype=torch.float32, device="cuda")
+    call("dl3_pwconv_fwd_rows", ptr(dev(xf), lxe), ldx, ptr(dev(s)) if s is not None else None,
+         ptr(dev(t)) if t is not None else None, a, ptr(dev(w)), ptr(dev(bias)), ptr(yfull, lye), ldy, M, K, N, None, 0, 1)
+    y = host(yfull)
+    assert np.abs(y[:, lye:] - ref).max() / np.abs(ref).max() < 1.5e-7
+    assert np.all(y[:, :lye] == 0)
+
+
+BD_FORM_ROUTES = [
+    # name, (M, K, N, two-tensor, add mode, stats), DL3_GEMM_PRE, route — the mask comes from the view's transform
+    ("stream_pre", (65536, 576, 192, False, 0, True), "1", R_TILED),   # 128x96 prefetching tiles (pw_gemm_stream_kernel EPI 2)
+    ("stream_nopre", (65536, 576, 192, False, 0, True), "0", R_TILED),
+    ("ws2_mode2", (65536 + 40, 320, 160, False, 0, True), None, R_WS_MFMA),
+    ("ksplit32", (2048, 160, 960, False, 0, True), None, R_KSPLIT),
+    # pw_ws2_kernel mode 3 (no diagnostic): the expand convolutions 64 -> 384, two-tensor dY, residual gradient
+    ("ws2_mode3", (131072 + 50, 64, 384, True, 1, True), None, None),
+]
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([(n, (c, p, r)) for n, c, p, r in BD_FORM_ROUTES]))
+def test_pwconv_bwd_data_transform_forms(L, case, form, act, monkeypatch):
+    """dl3_pwconv_bwd_data with the activation mask of each input transform (affine only: no mask; activation only: the
+    mask of x itself) on pw_gemm_stream_kernel with and without the prefetching epilogue, pw_ws2_kernel modes 2 and 3
+    and pw_ksplit32_kernel; BatchNorm-backward sums throughout"""
+    (M, K, N, two, addmode, stats), pre, route = case
+    if pre is not None:
+        monkeypatch.setenv("DL3_GEMM_PRE", pre)
+    if route is not None:
+        assert L.dl3_pwconv_route(1, M, K, N) == route
+    _bwd_data(L, M, K, N, act, two, addmode, stats, form=form)
+    release()
+
+
+BW_FORM_ROUTES = [
+    # name, (M, K, N, two-tensor, dbias), route direction (2: two-tensor dY, 4: single-tensor dY), route
+    ("tiled_single", (4096, 96, 576, False, True), 4, R_TILED),
+    ("tiled_two", (4096, 96, 576, True, False), 2, R_TILED),
+    ("row_single", (40000, 160, 960, False, False), 4, R_ROW),
+    ("row_two", (33000, 160, 328, True, False), 2, R_ROW),
+    ("narrow", (131072 + 5, 256, 21, False, True), 4, R_NARROW),
+]
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([(n, (c, d, r)) for n, c, d, r in BW_FORM_ROUTES]))
+def test_pwconv_bwd_weight_transform_forms(L, case, form, act):
+    """dl3_pwconv_bwd_weight under each input transform on pw_wgrad_kernel, pw_wgrad_row_kernel and pw_wgrad_narrow_kernel
+    (which rectified x only when a BatchNorm scale came with the activation: the act-only logits input of
+    Conv2D -> Activation -> Conv2D(classes) trained on the unrectified input)"""
+    (M, K, N, two, dbias), d, route = case
+    assert L.dl3_pwconv_route(d, M, K, N) == route
+    _bwd_weight(L, M, K, N, act, two, dbias, form=form)
+    release()
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([("tiled", ((2048, 960, 160), R_TILED)),
+                                                       ("row", ((33000, 160, 328), R_ROW))]))
+def test_pwconv_bwd_weight_dy_transform_forms(L, case, form, act):
+    """dl3_pwconv_bwd_weight_dy (two-tensor dY written once) under each input transform, tiled and one-tile-row kernels: the
+    weight gradient against float64 and bit for bit the one dl3_pwconv_bwd_weight computes"""
+    (M, K, N), route = case
+    assert L.dl3_pwconv_route(2, M, K, N) == route
+    test_pwconv_bwd_weight_writes_dy(L, (M, K, N, act, True, False, form))
+
+
+@pytest.mark.parametrize("case,form,act", _form_cases([("fused", (2048, 144, 24, True, False, 1)),
+                                                       ("fused_k64", (1500, 64, 64, True, True, 2))]))
+def test_pwconv_bwd_fused_transform_forms(L, case, form, act):
+    """dl3_pwconv_bwd_fused (pwfused.hip) under each input transform: weight gradient from the transformed input, data
+    gradient masked by the transform's activation"""
+    test_pwconv_bwd_fused(L, case[:3] + (act,) + case[3:] + (form,))
+
+
+BD_LAYOUTS = [
+    # name, (M, K, N, act, two-tensor, add mode, stats, form), {operand: (column offset, extra ld)}, route of the aligned shape
+    # strided, 16-byte aligned: the fast route still takes them
+    ("ws2_mode2-strided", (65536 + 40, 320, 160, 2, False, 0, True, "act"), {"x": (4, 8), "g": (4, 8), "dx": (8, 16)}, R_WS_MFMA),
+    ("ksplit32-two-strided-add", (2048, 160, 960, 1, True, 1, True, "affine+act"),
+     {"x": (32, 4), "g": (8, 12), "dx": (16, 48)}, R_KSPLIT),
+    ("stream-two-strided-add", (4096, 256, 144, 1, True, 1, True, "act"), {"x": (4, 0), "g": (16, 4), "dx": (4, 4)}, R_TILED),
+    # misaligned at the row count of pw_ws2_kernel: g at an odd float or an ld that is not a multiple of 4 -> pw_gemm_kernel
+    # with scalar loads on both operands (load mode 0); x at an odd float -> the stream kernel, mask read by scalar loads
+    ("ws2_rows-g_off1-gemm_mode0", (65536 + 40, 320, 160, 2, False, 0, True, "act"), {"g": (1, 0), "dx": (4, 4)}, R_WS_MFMA),
+    ("ws2_rows-ldg_odd-gemm_mode0", (65536 + 40, 320, 160, 1, False, 0, True, "affine+act"), {"g": (0, 1)}, R_WS_MFMA),
+    ("ws2_rows-x_off1-stream", (65536 + 40, 320, 160, 2, False, 0, True, "act"), {"x": (1, 0)}, R_WS_MFMA),
+    ("ksplit_rows-g_off1-gemm_mode0", (2048, 160, 960, 1, True, 1, True, "act"), {"g": (1, 2), "dx": (8, 8)}, R_KSPLIT),
+]
+
+
+@pytest.mark.parametrize("case,lay,route", [pytest.param(c, l, r, id=n) for n, c, l, r in BD_LAYOUTS])
+def test_pwconv_bwd_data_operand_layouts(L, case, lay, route):
+    """dl3_pwconv_bwd_data on the operands of engine.PwUnit.bwd: x a view into a wider buffer (ldx = inv.ld), g / yraw
+    from concat buffers (ldg, ldyraw), dx (and its residual addend) a channel slice of a wider buffer whose other columns
+    must stay untouched — and misaligned operands, which leave the 16-byte routes for the scalar-load fallbacks (the
+    load modes have no diagnostic: the test id names them)"""
+    M, K, N = case[:3]
+    assert L.dl3_pwconv_route(1, M, K, N) == route
+    _bwd_data(L, *case, lay=lay)
+
+
+BW_LAYOUTS = [
+    # name, (M, K, N, act, two-tensor, dbias, form), {operand: (column offset, extra ld)}, route direction, route
+    # strided, 16-byte aligned: the fast route still takes them
+    ("row_single-strided", (40000, 160, 960, 1, False, False, "act"), {"x": (4, 4), "g": (4, 4)}, 4, R_ROW),
+    ("row_two-strided", (33000, 160, 328, 2, True, False, "affine+act"), {"x": (4, 8), "g": (8, 4)}, 2, R_ROW),
+    ("narrow-strided", (131072 + 5, 256, 21, 1, False, True, "act"), {"x": (4, 8), "g": (3, 4)}, 4, R_NARROW),
+    ("tiled_two-strided", (4096, 96, 576, 2, True, False, "act"), {"x": (8, 4), "g": (4, 12)}, 2, R_TILED),
+    # misaligned at the row counts of the one-tile-row and narrow kernels -> pw_wgrad_kernel: g misaligned = load mode 2
+    # (16-byte loads on x only), x misaligned = load mode 0 (scalar loads on both)
+    ("row_single-g_off1-wgrad_mode2", (40000, 160, 960, 2, False, False, "act"), {"g": (1, 0)}, 4, R_ROW),
+    ("row_two-ldg_odd-wgrad_mode2", (33000, 160, 328, 1, True, False, "affine+act"), {"g": (0, 3)}, 2, R_ROW),
+    ("row_single-x_off1-wgrad_mode0", (40000, 160, 960, 1, False, False, "affine+act"), {"x": (1, 0)}, 4, R_ROW),
+    ("row_two-ldx_odd-wgrad_mode0", (33000, 160, 328, 2, True, False, "act"), {"x": (0, 1), "g": (4, 0)}, 2, R_ROW),
+    ("narrow-x_off1-wgrad_mode0", (131072 + 5, 256, 21, 1, False, True, "act"), {"x": (1, 0)}, 4, R_NARROW),
+    ("narrow-ldx_odd-wgrad_mode0", (131072 + 5, 256, 21, 2, False, True, "affine+act"), {"x": (0, 3)}, 4, R_NARROW),
+]
+
+
+@pytest.mark.parametrize("case,lay,d,route", [pytest.param(c, l, d, r, id=n) for n, c, l, d, r in BW_LAYOUTS])
+def test_pwconv_bwd_weight_operand_layouts(L, case, lay, d, route):
+    """dl3_pwconv_bwd_weight on the operands of engine.PwUnit.bwd (ldx = inv.ld, ldg / ldyraw of concat buffers): strided
+    aligned operands on the one-tile-row, narrow and tiled kernels, and misaligned ones at the row counts of the first two,
+    which take pw_wgrad_kernel in its load modes 2 and 0 (no diagnostic: the test id names them)"""
+    M, K, N = case[:3]
+    assert L.dl3_pwconv_route(d, M, K, N) == route
+    _bwd_weight(L, *case, lay=lay)
+    release()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the other ops that read a view: activation without BatchNorm (scale and shift NULL -> 1 and 0 in every kernel)
+@pytest.mark.parametrize("case", [pytest.param((2, 16, 20, 40, 1, 2, None, 2, 2, "act"), id="march-act-relu6"),
+                                  pytest.param((2, 15, 15, 24, 2, 1, None, 1, 1, "act"), id="gather-act-relu")])
+def test_dwconv_act_only(L, case):
+    """dl3_dwconv3x3_fwd / _bwd, march and gather kernels, on an activation-only view"""
+    test_dwconv_fwd(L, case)
+    test_dwconv_bwd(L, case)
+
+
+def _conv3x3_act_only(L, shape, act, mfma):
+    N, H, W, Cin, Cout, stride = shape
+    rng = np.random.default_rng(43)
+    Ho, pt, _ = O.same_pads(H, 3, stride, 1)
+    Wo, pl, _ = O.same_pads(W, 3, stride, 1)
+    x = rng.normal(0, 1, (N, H, W, Cin)).astype(np.float32)
+    w = rng.normal(0, 0.2, (3, 3, Cin, Cout)).astype(np.float32)
+    z = x.astype(np.float64)
+    xin = np_act(z, act)
+    tape = O.Tape()
+    wv = w.astype(np.float64)
+    ref = O.conv2d(xin, wv, stride, pt, pl, Ho, Wo, tape=tape)
+    geom = (N, H, W, Cin, Cout, stride, pt, pl, Ho, Wo)
+    xd, wd = dev(x), dev(w)
+    P = L.dl3_conv3x3_mfma_partials(N, Ho, Wo) if mfma else L.dl3_conv3x3_partials(N, Ho, Wo, Cout)
+    y, part = empty(N, Ho, Wo, Cout), empty(P, Cout, 2)
+    call("dl3_conv3x3_mfma_fwd" if mfma else "dl3_conv3x3_fwd", ptr(xd), None, None, act, ptr(wd), ptr(y), *geom, ptr(part))
+    assert relerr(host(y), ref) < TOL
+    s1, s2 = fold_partials(part, P, Cout)
+    assert relerr(s1, ref.sum((0, 1, 2))) < 1e-3 and relerr(s2, (ref ** 2).sum((0, 1, 2))) < 1e-3
+    g = rng.normal(0, 1, ref.shape).astype(np.float32)
+    cA, cB, cC = [rng.normal(0, 1, Cout).astype(np.float32) for _ in range(3)]
+    dY = cA * g.astype(np.float64) + cB * host(y) + cC
+    grads = tape.backward(ref, dY)
+    gd, cAd, cBd, cCd = dev(g), dev(cA), dev(cB), dev(cC)
+    if mfma:
+        wsb = L.dl3_conv3x3_mfma_bwd_weight_workspace(N, H, W, Cin, Cout, stride, Ho, Wo)
+        dw = empty(3, 3, Cin, Cout)
+        call("dl3_conv3x3_mfma_bwd_weight", ptr(xd), None, None, act, ptr(gd), ptr(y), ptr(cAd), ptr(cBd), ptr(cCd),
+             ptr(dw), *geom, ptr(empty((wsb + 3) // 4)), wsb)
+        dwg = host(dw)
+    else:
+        wpart = empty(P, 9 * Cin * Cout)
+        call("dl3_conv3x3_bwd_weight", ptr(xd), None, None, act, ptr(gd), ptr(y), ptr(cAd), ptr(cBd), ptr(cCd),
+             ptr(wpart), *geom)
+        dwg = host(wpart).astype(np.float64).sum(0).reshape(3, 3, Cin, Cout)
+    assert relerr(dwg, grads[id(wv)]) < 1e-3
+    if mfma:
+        wk = empty(Cout, 9 * Cin)
+        call("dl3_transpose", ptr(wd), ptr(wk), 9 * Cin, Cout)
+        P2 = L.dl3_conv3x3_mfma_partials(N, H, W)
+    else:
+        wk = wd
+        P2 = L.dl3_conv3x3_partials(N, H, W, Cin)
+    dx, dpart = empty(N, H, W, Cin), empty(P2, Cin, 2)
+    mean = rng.normal(0, 1, Cin).astype(np.float32)
+    invstd = rng.uniform(0.5, 2, Cin).astype(np.float32)
+    call("dl3_conv3x3_mfma_bwd_data" if mfma else "dl3_conv3x3_bwd_data", ptr(gd), ptr(y), ptr(cAd), ptr(cBd), ptr(cCd),
+         ptr(wk), ptr(dx), ptr(xd), None, None, act, None, ptr(dev(mean)), ptr(dev(invstd)), ptr(dpart), *geom)
+    dx_ref = grads[id(xin)] * np_mask(z, act)
+    assert relerr(host(dx), dx_ref) < TOL
+    d1, d2 = fold_partials(dpart, P2, Cin)
+    assert relerr(d1, dx_ref.sum((0, 1, 2))) < 1e-3
+    assert relerr(d2, (dx_ref * (x - mean) * invstd).sum((0, 1, 2))) < 1e-3
+
+
+@pytest.mark.parametrize("shape,act,mfma", [pytest.param((1, 16, 16, 32, 64, 1), 1, False, id="direct-act-relu"),
+                                            pytest.param((1, 17, 19, 32, 64, 2), 2, True, id="mfma-act-relu6")])
+def test_conv3x3_act_only(L, shape, act, mfma):
+    """dl3_conv3x3_* (direct vector-ALU kernels, and the MFMA kernels) on an activation-only view: forward + sums, weight
+    gradient, bwd-data with the activation mask of x itself + BatchNorm-backward sums"""
+    _conv3x3_act_only(L, shape, act, mfma)
+
+
+@pytest.mark.parametrize("act", [1, 2], ids=["relu", "relu6"])
+def test_gap_and_subsample_act_only(L, act):
+    """dl3_gap_fwd and dl3_subsample_fwd on an activation-only view (reading a channel slice)"""
+    rng = np.random.default_rng(44)
+    B, HW, C, off = 2, 128, 48, 16
+    xf = rng.normal(0.5, 2, (B * HW, C + off)).astype(np.float32)
+    o = empty(B, C)
+    call("dl3_gap_fwd", ptr(dev(xf), off), C + off, None, None, act, ptr(o), B, HW, C, 1.0 / HW)
+    assert relerr(host(o), np_act(xf[:, off:].astype(np.float64), act).reshape(B, HW, C).mean(1)) < 1e-5
+    N, H, W, s_ = 2, 9, 10, 2
+    Ho, Wo = (H - 1) // s_ + 1, (W - 1) // s_ + 1
+    x = rng.normal(0.5, 4, (N, H, W, C)).astype(np.float32)
+    y = empty(N, Ho, Wo, C)
+    call("dl3_subsample_fwd", ptr(dev(x)), C, None, None, act, ptr(y), N, H, W, C, s_, Ho, Wo)
+    assert np.array_equal(host(y), np_act(x[:, ::s_, ::s_], act))

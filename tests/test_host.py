@@ -584,6 +584,53 @@ def test_default_kernel_routes_by_name(monkeypatch):
     assert L.dl3_pwconv_partials(M, 160, 960) >= 42 and L.dl3_pwconv_partials(M, 960, 160) >= 42
 
 
+def test_weight_gradient_route_follows_the_operand_form():
+    """dl3_pwconv_route dir 2 (two-tensor dY) and dir 4 (single-tensor dY) pick the tile configuration the way the launch
+    does (pick_wgrad(M, K, N, two)): at 32 768 x 80 x 448 the two-tensor pick fits one tile row, the single-tensor one does
+    not; where both picks agree, so do the directions; the logits layer's narrow kernel exists for the single-tensor form only"""
+    from dl3_amd import capi
+    L = capi.lib()
+    R = dict(tiled=0, wgrad_row=4, narrow=5)
+    assert L.dl3_pwconv_route(2, 32768, 80, 448) == R["wgrad_row"] and L.dl3_pwconv_route(4, 32768, 80, 448) == R["tiled"]
+    for M, K, N in ((40000, 160, 960), (40009, 96, 576), (33000, 160, 328), (32771, 96, 576)):
+        assert L.dl3_pwconv_route(2, M, K, N) == L.dl3_pwconv_route(4, M, K, N) == R["wgrad_row"]
+    assert L.dl3_pwconv_route(4, 131072, 256, 21) == R["narrow"] and L.dl3_pwconv_route(2, 131072, 256, 21) == R["tiled"]
+
+
+def _act_only_logits_model(G, H=256, W=256, cin=8, classes=21):
+    """Input -> Conv2D(256, 1) -> Activation("relu") -> Conv2D(classes, 1) -> softmax: the logits convolution reads a view
+    with an activation and no BatchNorm"""
+    G.clear_session(seed=7)
+    inp = G.Input(shape=(H, W, cin))
+    x = G.Conv2D(256, 1, name="c0")(inp)
+    x = G.Activation("relu")(x)
+    x = G.Conv2D(classes, 1, use_bias=True, name="logits")(x)
+    x = G.Reshape((H * W, -1))(x)
+    x = G.Activation("softmax", name="pred_mask")(x)
+    return G.Model(inp, x, name="act_only_logits")
+
+
+def test_act_only_view_reaches_the_narrow_weight_gradient(monkeypatch):
+    """the plan of _act_only_logits_model at B = 2, lowered without a GPU: the logits layer's weight gradient is ONE
+    dl3_pwconv_bwd_weight launch over 131 072 rows with in_scale = in_shift = NULL and in_act = RELU, on the narrow route
+    (pw_wgrad_narrow_kernel) — the launch tests/test_gpu_model.py checks against float64 — and its bwd-data carries the
+    activation-only mask"""
+    import torch
+    from dl3_amd.engine import Engine
+    L = capi.lib()
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    e = Engine(_act_only_logits_model(G), batch=2, training=True, device="cpu")
+    wg = [op[2] for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_weight" and op[2][15:17] == [256, 21]]
+    assert len(wg) == 1
+    a = wg[0]
+    assert a[2] is None and a[3] is None and a[4] == capi.ACT_RELU and a[14] == 131072
+    assert a[12] is not None and a[13] is not None            # dw and the bias gradient: folded by the launch
+    assert L.dl3_pwconv_route(4, a[14], a[15], a[16]) == 5
+    bd = [op[2] for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_data" and op[2][22:25] == [131072, 256, 21]]
+    assert len(bd) == 1 and bd[0][10] is not None and bd[0][12] is None and bd[0][13] is None and bd[0][14] == capi.ACT_RELU
+
+
 def test_benchmarked_plan_lowers_consistently_without_a_gpu(monkeypatch):
     """the plan bench.py times (cfg2, B=128) and its small-batch / frozen / data-parallel / Xception relatives, lowered on
     the CPU: kernel routes of round 5 (12 both-gradient launches incl. the six-block 32 <-> 192 layers, 12 forward

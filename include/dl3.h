@@ -397,6 +397,25 @@ int dl3_prepare_targets(const void *labels, int label_dtype, int B, int HW, int 
  * (utils.Jaccard_from_counts): union = true + pred - inter, exactly the reference's inter/union sums. */
 int dl3_seg_counts(const int *pred, const float *y_true, int B, int HW, int C, int *counts, void *stream);
 
+/* ---- training augmentation (SegmentationGenerator.__getitem__, utils.py:310-369) ------------------------------------
+ * images[B][Hs][Ws][3] uint8 (BGR) and labels[B][Hs][Ws] (label_dtype) -> X[B][H][W][3] float32 (the engine's input) and
+ * labels_out[B][H][W] (label_dtype; with DL3_AUG_WARP uint8, values the interpolation created set to C = void).
+ * Per image, in the reference's order: [blur 5x5] -> crop at (x, y) -> [hflip] -> [vflip] -> gamma LUT -> [warpAffine]
+ * -> [CLAHE on Y of YUV].  Every floating-point decision is taken on the host (augment.py) and arrives as tables:
+ *   img_params[B][8] = {blur_on, crop_x, crop_y, hflip, vflip, 0, 0, 0};  lut[B][256] (identity without brightness)
+ *   warp_tab[B][2W + 2H] = adelta[W], bdelta[W], X0[H], Y0[H] (cv2 fixed point, +16 rounding in X0 / Y0; identity
+ *                          tables when only DL3_AUG_CLAHE is set)
+ *   clahe_i[2W + 2H] = (tx1, tx2) per x then (ty1, ty2) per y;  clahe_f[2W + 2H] = (xa, 1-xa) per x, (ya, 1-ya) per y
+ * Without DL3_AUG_WARP / DL3_AUG_CLAHE stage 1 writes X directly.  The warp takes uint8 labels only (-4 otherwise);
+ * H >= 3, W >= 3, H <= Hs, W <= Ws, C <= 255 with the warp (-1 otherwise); CLAHE needs H, W >= 16 (-4).
+ * Integer atomics only. */
+#define DL3_AUG_WARP 1
+#define DL3_AUG_CLAHE 2
+size_t dl3_augment_workspace_bytes(int B, int H, int W, int flags);
+int dl3_augment(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H, int W, int flags,
+                const int *img_params, const int *lut, const int *warp_tab, const int *clahe_i, const float *clahe_f,
+                int C, float *X, void *labels_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

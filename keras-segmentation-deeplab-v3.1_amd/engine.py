@@ -1344,7 +1344,13 @@ class Engine:
         """one step on (x, y, sw).  Data parallel (external_nnz): ONE loss over the global batch,
         L = sum_all(l*w) / count_all(w != 0) — every rank differentiates sum_shard(l*w) / c0, the all-reduce sums
         gradients, counts and loss sums, Adam applies c0 / count_all on the device: nothing in front of the captured
-        step, one collective behind it, no host round trip.  lazy: the loss comes back as a LazyLoss (no device read)."""
+        step, one collective behind it, no host read.  lazy: the loss comes back as a LazyLoss (no device read).
+        The host waits for the stream to drain before it enqueues the step: a replay of the captured step enqueued
+        behind a pageable device-to-host copy of ~100 KB or more (any `.cpu()` / `.numpy()` read-back between two steps)
+        computed a wrong step on the MI355X runtime (tests/test_gpu_augment.py::test_host_read_back_between_steps); an
+        event wait on the stream did not help, a host-side stream synchronisation does.  The next batch is prepared on
+        the host before this call, so that work still overlaps the previous step."""
+        torch.cuda.current_stream().synchronize()
         self.set_input(x)
         self.set_targets(y, sw)
         self.fwd_bwd()

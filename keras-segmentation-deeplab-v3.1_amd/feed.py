@@ -8,6 +8,10 @@ tensors per step (335 MB at B=64).  Here a batch is 1 byte per pixel-channel + 1
     host (pinned)  --copy stream-->  device slot (uint8)  --compute stream-->  engine.xbuf (float32, widened),
                                                                              engine.labels / .sweights (dl3_prepare_targets)
 
+Augmenting generators (utils.SegmentationGenerator with any augmentation keyword on): the slots hold the SOURCE-sized
+bytes plus one int32 table upload per batch (augment.tables), and consume() runs dl3_augment (blur / crop / flips / gamma
+LUT / warp / CLAHE, straight into engine.xbuf and an augmented label slot) instead of the widening copy.
+
 Two device slots: while step i runs from slot i % 2 (already widened into the engine's own buffers), batch i+1 lands in the
 other one.  The compute stream waits for a slot's copy event before it reads it; the copy stream waits for the slot's
 consume event before it overwrites it.  The host never waits for a step: its only wait is for the H2D copy a slot issued
@@ -21,7 +25,7 @@ from .capi import ptr
 
 
 class BatchFeeder:
-    def __init__(self, eng, n_classes, label_dtype=np.uint8, slots=2):
+    def __init__(self, eng, n_classes, label_dtype=np.uint8, slots=2, plan=None):
         if not eng.training:
             raise ValueError("BatchFeeder feeds a training engine (images + label maps)")
         if label_dtype not in (np.uint8, np.int32):
@@ -29,6 +33,13 @@ class BatchFeeder:
         self.eng, self.C, self.slots = eng, int(n_classes), int(slots)
         self.M = eng.logits_view.buf.M                    # label pixels per batch
         self.nx = eng.xbuf.t.numel()                      # image bytes per batch
+        self.plan = plan if plan is not None and plan.active else None
+        if self.plan is not None:                         # augmenting: the slots hold the (larger) source
+            if eng.B * self.plan.H * self.plan.W * 3 != self.nx:
+                raise ValueError("augmented %dx%d images do not fit the engine's input (%d floats per batch)"
+                                 % (self.plan.H, self.plan.W, self.nx))
+            src = eng.B * self.plan.Hs * self.plan.Ws
+            self.M_out, self.M, self.nx = self.M, src, 3 * src
         self.ldtype = torch.uint8 if label_dtype == np.uint8 else torch.int32
         self.lcode = capi.LABEL_U8 if label_dtype == np.uint8 else capi.LABEL_I32
         dev = eng.device
@@ -37,6 +48,13 @@ class BatchFeeder:
         self.hx = [torch.empty(self.nx, dtype=torch.uint8).pin_memory() for _ in range(self.slots)]
         self.hl = [torch.empty(self.M, dtype=self.ldtype).pin_memory() for _ in range(self.slots)]
         self.hist = torch.empty(eng.B, self.C + 1, dtype=torch.int32, device=dev)
+        if self.plan is not None:
+            from . import augment
+            self.dlab = torch.empty(self.M_out, dtype=self.ldtype, device=dev)      # the augmented label maps
+            self.ws = torch.empty(augment.workspace_bytes(self.plan, eng.B), dtype=torch.uint8, device=dev)
+            self.dtab = [None] * self.slots
+            self.htab = [None] * self.slots
+            self.offs = [None] * self.slots
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.ready = [torch.cuda.Event() for _ in range(self.slots)]     # the slot's H2D copy has landed
         self.free = [torch.cuda.Event() for _ in range(self.slots)]      # the slot has been consumed
@@ -79,17 +97,31 @@ class BatchFeeder:
         like.numpy()[...] = np.ascontiguousarray(a).reshape(-1)
         return like
 
-    def stage(self, slot, images, labels):
-        """enqueue batch (images uint8 [B,H,W,3], labels [B,H,W] or [B,HW]) for `slot` on the copy stream"""
+    def stage(self, slot, images, labels, params=None):
+        """enqueue batch (images uint8 [B,H,W,3], labels [B,H,W] or [B,HW]; params: the augment.ImageParams of every
+        image when augmenting) for `slot` on the copy stream"""
+        if (self.plan is not None) != (params is not None):
+            raise ValueError("device feed: an augmenting feeder takes (images, labels, params), a plain one (images, labels)")
         if self._used[slot]:
             self.ready[slot].synchronize()   # (the slot's previous H2D copy, two steps old, has left its pinned buffer)
         hx, hl = self._pinned(images, self.hx[slot], "images"), self._pinned(labels, self.hl[slot], "labels")
         assert hx.numel() == self.nx and hl.numel() == self.M, (hx.numel(), self.nx, hl.numel(), self.M)
+        if params is not None:
+            from . import augment
+            if len(params) != self.eng.B:
+                raise ValueError("device feed: %d augmentation parameter sets for %d images" % (len(params), self.eng.B))
+            tab, self.offs[slot] = augment.tables(self.plan, params)
+            if self.htab[slot] is None or self.htab[slot].numel() != tab.size:
+                self.htab[slot] = torch.empty(tab.size, dtype=torch.int32).pin_memory()
+                self.dtab[slot] = torch.empty(tab.size, dtype=torch.int32, device=self.eng.device)
+            self.htab[slot].numpy()[...] = tab
         with torch.cuda.stream(self.copy_stream):
             if self._used[slot]:
                 self.copy_stream.wait_event(self.free[slot])
             self.dx[slot].copy_(hx, non_blocking=True)
             self.dl[slot].copy_(hl, non_blocking=True)
+            if params is not None:
+                self.dtab[slot].copy_(self.htab[slot], non_blocking=True)
             self.ready[slot].record(self.copy_stream)
 
     def consume(self, slot):
@@ -97,14 +129,22 @@ class BatchFeeder:
         eng = self.eng
         st = torch.cuda.current_stream()
         st.wait_event(self.ready[slot])
-        eng.xbuf.t.copy_(self.dx[slot])                                   # uint8 -> float32 on the device
-        capi.call("dl3_prepare_targets", ptr(self.dl[slot]), self.lcode, eng.B, self.M // eng.B, self.C, ptr(eng.labels),
+        if self.plan is None:
+            eng.xbuf.t.copy_(self.dx[slot])                               # uint8 -> float32 on the device
+            lab, M = self.dl[slot], self.M
+        else:
+            from . import augment
+            B, (Hs, Ws) = eng.B, (self.plan.Hs, self.plan.Ws)
+            augment.launch(self.plan, self.dtab[slot], self.offs[slot], self.dx[slot].view(B, Hs, Ws, 3),
+                           self.dl[slot].view(B, Hs, Ws), self.C, eng.xbuf.t, self.dlab, self.ws, st.cuda_stream)
+            lab, M = self.dlab, self.M_out
+        capi.call("dl3_prepare_targets", ptr(lab), self.lcode, eng.B, M // eng.B, self.C, ptr(eng.labels),
                   ptr(eng.sweights), ptr(self.hist), st.cuda_stream)
         self.free[slot].record(st)
         self._used[slot] = True
 
     def run(self, batches, step):
-        """the pipelined loop: batches = iterable of (images, labels); step() = the resident step (fwd_bwd + Adam)"""
+        """the pipelined loop: batches = iterable of (images, labels[, params]); step() = the resident step (fwd_bwd + Adam)"""
         it = iter(batches)
         nxt = next(it, None)
         if nxt is None:

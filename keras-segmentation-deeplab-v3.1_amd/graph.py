@@ -693,7 +693,8 @@ class Model:
         device_feed=True (not in Keras): the generator yields (uint8 images [B,H,W,3], raw label maps [B,H,W] uint8 / int32)
         — what cv2 decodes, before SegmentationGenerator.__getitem__ turns it into float tensors (utils.py:375-402): the
         batch crosses PCIe as bytes on a copy stream while the previous step runs, and X / Y / SW are produced on the device
-        (feed.BatchFeeder: widening copy + dl3_prepare_targets).
+        (feed.BatchFeeder: widening copy + dl3_prepare_targets).  A utils.SegmentationGenerator is read through its
+        raw_batch(i): with augmentation on, the feeder runs dl3_augment on the device instead of the widening copy.
         Under distribute() (utils.py:209-211 + :231-241): global_batch=True — the generator yields the GLOBAL batch and each
         rank stages only its contiguous shard (rows dp.shard(n)) — or global_batch=False — the generator is already sharded
         by rank (e.g. `idx[rank::world]`) and yields this rank's images only.  Either way only the shard crosses PCIe."""
@@ -722,19 +723,28 @@ class Model:
         opt = (self._compiled or {}).get("optimizer") or {}
         C = int(n_classes if n_classes is not None else self.output.shape[-1])
         hist, feeders = [], {}
+        # utils.SegmentationGenerator: raw_batch() gives the source bytes (+ augmentation parameters) of a batch
+        raw = hasattr(generator, "raw_batch")
+        plan = getattr(generator, "plan", None) if raw else None
         for _ in range(epochs):
             def batches():
                 for i in range(steps):
-                    item = generator[i] if hasattr(generator, "__getitem__") else next(generator)
-                    X, L = np.asarray(item[0]), np.asarray(item[1])
+                    if raw:
+                        # the augmentation parameters of the WHOLE global batch are drawn before a rank keeps its shard:
+                        # the global batch is the one a single GPU would train on
+                        X, L, P = generator.raw_batch(i)
+                    else:
+                        item = generator[i] if hasattr(generator, "__getitem__") else next(generator)
+                        X, L, P = item[0], item[1], None
+                    X, L = np.asarray(X), np.asarray(L)
                     if dp is not None and global_batch:
                         # the rank's contiguous shard of the global batch (the remainder of a batch that does not divide goes
                         # to the last rank, like multi_gpu_model's last tower): only these rows are staged and copied
                         if X.shape[0] < dp.world:
                             raise ValueError("global batch of %d images cannot be split over %d ranks" % (X.shape[0], dp.world))
                         lo, hi = dp.shard(X.shape[0])
-                        X, L = X[lo:hi], L[lo:hi]
-                    yield X, L
+                        X, L, P = X[lo:hi], L[lo:hi], (P[lo:hi] if P is not None else None)
+                    yield (X, L) if P is None else (X, L, P)
             losses = []
             it = iter(batches())
             first = next(it, None)
@@ -745,7 +755,7 @@ class Model:
                 self._dp_sync_weights(eng)
             key = (id(eng), first[1].dtype.str)
             if key not in feeders:
-                feeders[key] = BatchFeeder(eng, C, np.uint8 if first[1].dtype == np.uint8 else np.int32)
+                feeders[key] = BatchFeeder(eng, C, np.uint8 if first[1].dtype == np.uint8 else np.int32, plan=plan)
 
             def chain():
                 yield first

@@ -6,7 +6,9 @@ dl3_softmax_xent — and host restatements of the metrics that the north star le
 Next-ring rows of SURVEY §8(f): `prepare_targets` (N2, the label half of SegmentationGenerator.__getitem__ on the
 device) and `Jaccard_from_counts` / `accuracy_from_counts` (N3, metrics from dl3_seg_counts).
 `do_crf` (N4) is the host hook with the reference's parameters; it needs the optional pydensecrf package.
-Out of scope by the SURVEY §8 contract: image file I/O + cv2 augmentation, plotting.
+The cv2 augmentation chain (utils.py:319-365) runs on the device (augment.py, dl3_augment) behind
+SegmentationGenerator's augmentation keywords and SegModel.create_generators.
+Out of scope by the SURVEY §8 contract: image file I/O, plotting.
 """
 import numpy as np
 
@@ -144,12 +146,23 @@ def do_crf(im, mask, zero_unsure=True):
 class SegmentationGenerator:
     """The tensor contract of the reference's `SegmentationGenerator` (utils.py:257-409) over IN-MEMORY arrays:
     `gen[i]` -> `(X [B,H,W,3] float32, Y [B,HW,1], {'pred_mask': SW [B,HW]})`, `len(gen)` batches, `on_epoch_end()`
-    reshuffles.  File I/O and the cv2 augmentation chain of the reference (utils.py:314-369) are out of scope: the caller
-    hands over decoded images (raw 0-255, as `self.X[n] = image`, utils.py:387) and raw label maps; the label half
-    (utils.py:371-400) runs on the device through dl3_prepare_targets, so Y and SW are cuda tensors that
-    `Model.fit_generator` / `train_on_batch` consume without a host round trip."""
+    reshuffles.  File I/O is out of scope: the caller hands over decoded images (raw 0-255 BGR, as
+    `self.X[n] = image`, utils.py:387) and raw label maps; the label half (utils.py:371-400) runs on the device through
+    dl3_prepare_targets, so Y and SW are cuda tensors that `Model.fit_generator` / `train_on_batch` consume without a host
+    round trip.
 
-    def __init__(self, images, labels, n_classes=21, batch_size=1, seed=7, shuffle=True):
+    Augmentation (utils.py:319-365): the reference's keywords `resize_shape, crop_shape, horizontal_flip, vertical_flip,
+    blur, brightness, rotation, zoom, do_ahisteq` (cv2 (width, height) order for the shapes), all OFF by default.  With
+    any of them on, images must be uint8, the per-image parameters come from one `random.Random(seed)` in the
+    reference's call order (augment.Plan.draw; `on_epoch_end` shuffles with the same stream, as the reference's global
+    `random` does), and the chain runs on the device (dl3_augment): X comes back as host float32, Y / SW stay on the
+    device.  `raw_batch(i)` hands the same batch to the device feed before augmentation."""
+
+    def __init__(self, images, labels, n_classes=21, batch_size=1, seed=7, shuffle=True, resize_shape=None,
+                 crop_shape=None, horizontal_flip=False, vertical_flip=False, blur=0, brightness=0.0, rotation=0.0,
+                 zoom=0.0, do_ahisteq=False):
+        import random
+        from . import augment
         self.images = np.asarray(images)
         self.labels = np.asarray(labels)
         if self.images.ndim != 4 or self.images.shape[-1] != 3 or len(self.images) != len(self.labels):
@@ -159,21 +172,67 @@ class SegmentationGenerator:
         self.shuffle = shuffle
         self._rng = np.random.RandomState(seed)
         self.order = np.arange(len(self.images))
+        self.plan = augment.Plan(self.images.shape[1:3], resize_shape, crop_shape, horizontal_flip, vertical_flip, blur,
+                                 brightness, rotation, zoom, do_ahisteq)
+        self.random = random.Random(seed)
+        if self.plan.active:
+            if self.images.dtype != np.uint8:
+                raise ValueError("augmentation reads decoded uint8 images, got %s" % self.images.dtype)
+            if self.labels.dtype not in (np.uint8, np.int32):
+                raise ValueError("augmentation reads uint8 / int32 label maps, got %s" % self.labels.dtype)
+            if self.plan.warp and self.labels.dtype != np.uint8:
+                raise ValueError("rotation / zoom warp the label map as uint8 (cv2.warpAffine, utils.py:353): "
+                                 "int32 label maps cannot be warped")
 
     def __len__(self):
         return len(self.images) // self.batch_size
 
-    def __getitem__(self, i):
+    def _index(self, i):
         if not 0 <= i < len(self):
             raise IndexError(i)
-        idx = self.order[i * self.batch_size:(i + 1) * self.batch_size]
-        X = np.ascontiguousarray(self.images[idx], dtype=np.float32)
-        Y, SW = prepare_targets(self.labels[idx], self.n_classes)
-        return X, Y, {"pred_mask": SW}
+        return self.order[i * self.batch_size:(i + 1) * self.batch_size]
+
+    def raw_batch(self, i):
+        """(uint8 images [B,Hs,Ws,3], label maps [B,Hs,Ws], params) of batch i before augmentation; params is the list
+        of augment.ImageParams drawn for it (None when no augmentation is on)"""
+        idx = self._index(i)
+        params = [self.plan.draw(self.random) for _ in idx] if self.plan.active else None
+        return self.images[idx], self.labels[idx], params
+
+    def __getitem__(self, i):
+        if not self.plan.active:
+            idx = self._index(i)
+            X = np.ascontiguousarray(self.images[idx], dtype=np.float32)
+            Y, SW = prepare_targets(self.labels[idx], self.n_classes)
+            return X, Y, {"pred_mask": SW}
+        import torch
+        from . import augment
+        images, labels, params = self.raw_batch(i)
+        plan, B = self.plan, len(params)
+        tab, offs = augment.tables(plan, params)
+        ldt = torch.uint8 if labels.dtype == np.uint8 else torch.int32
+        if getattr(self, "_dev", None) is None or self._dev[0] != (B, tab.size, ldt):
+            # device buffers of one batch, allocated once and reused by every batch of this generator
+            self._dev = ((B, tab.size, ldt), torch.empty(tab.size, dtype=torch.int32, device="cuda"),
+                         torch.empty(images.shape, dtype=torch.uint8, device="cuda"),
+                         torch.empty(labels.shape, dtype=ldt, device="cuda"),
+                         torch.empty(B, plan.H, plan.W, 3, dtype=torch.float32, device="cuda"),
+                         torch.empty(B, plan.H * plan.W, dtype=ldt, device="cuda"),
+                         torch.empty(augment.workspace_bytes(plan, B), dtype=torch.uint8, device="cuda"))
+        _, dtab, dimg, dlab, X, L, ws = self._dev
+        dtab.copy_(torch.from_numpy(tab))
+        dimg.copy_(torch.from_numpy(np.ascontiguousarray(images)))
+        dlab.copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        augment.launch(plan, dtab, offs, dimg, dlab, self.n_classes, X, L, ws)
+        Y, SW = prepare_targets(L, self.n_classes)
+        return X.cpu().numpy(), Y, {"pred_mask": SW}
 
     def on_epoch_end(self):
         if self.shuffle:
-            self._rng.shuffle(self.order)
+            if self.plan.active:
+                self.random.shuffle(self.order)    # utils.py:404-408: the stream the augmentation draws from
+            else:
+                self._rng.shuffle(self.order)
 
 
 class SegModel:
@@ -228,6 +287,31 @@ class SegModel:
                               RuntimeWarning, stacklevel=2)
         self.model = model
         return model
+
+    def create_generators(self, crop_shape=False, mode="train", do_ahisteq=True, n_classes=21, horizontal_flip=True,
+                          vertical_flip=False, blur=False, with_bg=True, brightness=0.1, rotation=5.0, zoom=0.1,
+                          validation_split=.2, seed=7, images=None, labels=None):
+        """utils.py:216-226 over in-memory arrays (this package reads no files): `images` uint8 [N,H,W,3] in cv2's BGR
+        order at the model's size (or larger, with crop_shape), `labels` uint8 / int32 [N,H,W].  mode 'train' /
+        'validation' split as the reference does (utils.py:268-276): np.random.seed(seed); the first
+        round(N * validation_split) of permutation(N) validate, the sorted rest trains.  with_bg is accepted and ignored,
+        as in the reference."""
+        if mode not in ("train", "validation"):
+            raise ValueError("create_generators: mode %r is not supported (the reference's 'test' mode reads the test "
+                             "JPEG folder; this package reads no files)" % (mode,))
+        if images is None or labels is None:
+            raise ValueError("create_generators: pass the decoded data as images= (uint8 [N,H,W,3], BGR) and labels= "
+                             "(uint8 / int32 [N,H,W]); reading the dataset folder %r (JPEG decode) is out of scope"
+                             % (self.mainpath,))
+        images, labels = np.asarray(images), np.asarray(labels)
+        n = len(images)
+        x = np.random.RandomState(seed).permutation(n)[:round(n * validation_split)]
+        if mode == "train":
+            x = np.setxor1d(x, np.arange(n))
+        return SegmentationGenerator(images[x], labels[x], n_classes=n_classes, batch_size=self.batch_size, seed=seed,
+                                     resize_shape=self.sz[::-1], crop_shape=crop_shape, horizontal_flip=horizontal_flip,
+                                     vertical_flip=vertical_flip, blur=blur, brightness=brightness, rotation=rotation,
+                                     zoom=zoom, do_ahisteq=do_ahisteq)
 
     def load_weights(self, model):
         model.load_weights(self.modelpath)

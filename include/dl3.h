@@ -416,6 +416,25 @@ int dl3_augment(const void *images, const void *labels, int label_dtype, int B, 
                 const int *img_params, const int *lut, const int *warp_tab, const int *clahe_i, const float *clahe_f,
                 int C, float *X, void *labels_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- dense-CRF post-processing (do_crf, utils.py:74-91): exact mean-field inference, DESIGN.md §9 -----------------------
+ * The model the reference configures in pydensecrf — unary from labels, a Gaussian position kernel and a bilateral
+ * position + colour kernel, both with symmetric normalisation, Potts compatibility — evaluated over ALL pixel pairs
+ * (no permutohedral lattice).  fp32, fixed summation order, no float atomics; L <= 32 labels (-4 above).
+ * One workspace serves both launches: dl3_crf_workspace_bytes(B, H, W, L) (for dl3_crf_message: H * W >= N); 16-byte
+ * aligned.
+ * dl3_crf_message: one un-normalised pass out[b][i][l] = sum_j exp(-|f_i - f_j|^2 / 2) * Qin[b][j][l] (the j = i term
+ *   included) over features feat[B][N][D], D <= 6 (-4 above); Qin and out are [B][N][L].
+ * dl3_crf_inference: im[B][H][W][3] uint8, U[B][L][N] unary energies (N = H*W, pixel i = y*W + x),
+ *   params = {sx, sy, w_gauss, sxy, srgb, w_bilateral}, six floats in HOST memory read before the call returns;  features g_i = (x/sx, y/sy), b_i = (x/sxy, y/sxy, c/srgb),
+ *   k_ij = exp(-|f_i - f_j|^2 / 2), n_i = 1/sqrt(sum_j k_ij + 1e-20), M(Q)_i = n_i sum_j k_ij n_j Q_j;
+ *   Q = softmax(-U); iters times Q = softmax(-U + w_gauss M_g(Q) + w_bilateral M_b(Q)).  Outputs, each nullable:
+ *   Q[B][L][N], energy[B][L][N] (the last update's pre-softmax values), map[B][N] (int32 argmax, first maximum). */
+size_t dl3_crf_workspace_bytes(int B, int H, int W, int L);
+int dl3_crf_message(const float *feat, int D, const float *Qin, int B, int N, int L, float *out, void *ws,
+                    size_t ws_bytes, void *stream);
+int dl3_crf_inference(const unsigned char *im, const float *U, int B, int H, int W, int L, const float *params,
+                      int iters, float *Q, float *energy, int *map, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

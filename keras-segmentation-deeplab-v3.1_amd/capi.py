@@ -25,6 +25,7 @@ _CTYPES = {
     "const int *": ctypes.c_void_p,
     "void *": ctypes.c_void_p,
     "const void *": ctypes.c_void_p,
+    "const unsigned char *": ctypes.c_void_p,
     "void * *": ctypes.POINTER(ctypes.c_void_p),
     "const long long *": ctypes.c_void_p,
     "unsigned long long *": ctypes.c_void_p,

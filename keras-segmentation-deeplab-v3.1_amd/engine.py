@@ -1198,11 +1198,13 @@ class Engine:
             self.run_ops([self._shuffle_op])  # nor does the fused Subpixel tail
         return v.buf.t.cpu().numpy().reshape(self.B, v.buf.H, v.buf.W, v.C)
 
-    def argmax(self):
+    def argmax(self, host=True):
+        """int32 masks [B,H,W]: a numpy array, or with host=False the device tensor"""
         v = self.logits_view
         out = torch.empty(v.buf.M, dtype=torch.int32, device=self.device)
         capi.call("dl3_argmax", ptr(v.buf.t), out.data_ptr(), v.buf.M, v.C, torch.cuda.current_stream().cuda_stream)
-        return out.cpu().numpy().reshape(self.B, v.buf.H, v.buf.W)
+        out = out.reshape(self.B, v.buf.H, v.buf.W)
+        return out.cpu().numpy() if host else out
 
     def set_targets(self, y, sw=None):
         """labels [B,HW,1] (void = classes) and temporal sample weights [B,HW]; numpy arrays or device tensors (e.g. the

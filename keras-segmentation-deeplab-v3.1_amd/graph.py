@@ -574,10 +574,13 @@ class Model:
             outs.append(eng.predict(xb))
         return np.concatenate(outs, axis=0)
 
-    def predict_mask(self, x, batch_size=32):
+    def predict_mask(self, x, batch_size=32, crf=False):
         """np.argmax(model.predict(x), -1) (notebook cell 9) without shipping the probabilities to the host: the argmax
         runs on the device (dl3_argmax) and only the int32 masks [B,H,W] cross PCIe — 1 MB instead of 22 MB per
-        512x512x21 image.  Not part of the reference's Model API."""
+        512x512x21 image.  Not part of the reference's Model API.
+
+        crf=True: the notebook's `do_crf(image, mask)` step on the device as well — every batch's masks go through
+        crf.dense_crf with `x` as the image (zero_unsure=True, the reference's default) before they are copied out."""
         if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
             x = np.asarray(x, np.float32)
         n = x.shape[0]
@@ -588,7 +591,11 @@ class Model:
             eng = self._engine(xb.shape[0], False)
             eng.set_input(xb)
             eng.forward()
-            outs.append(eng.argmax())
+            if crf:
+                from .crf import dense_crf
+                outs.append(dense_crf(xb, eng.argmax(host=False)).to("cpu").numpy().astype(np.int32))
+            else:
+                outs.append(eng.argmax())
         return np.concatenate(outs, axis=0)
 
     def evaluate(self, x, y, batch_size=32, sample_weight=None, verbose=0):

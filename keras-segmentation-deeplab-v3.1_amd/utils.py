@@ -5,7 +5,8 @@ dl3_softmax_xent — and host restatements of the metrics that the north star le
 (`Jaccard` utils.py:139-157, `sparse_accuracy_ignoring_last_label` utils.py:132-138).
 Next-ring rows of SURVEY §8(f): `prepare_targets` (N2, the label half of SegmentationGenerator.__getitem__ on the
 device) and `Jaccard_from_counts` / `accuracy_from_counts` (N3, metrics from dl3_seg_counts).
-`do_crf` (N4) is the host hook with the reference's parameters; it needs the optional pydensecrf package.
+`do_crf` (N4) is the host hook with the reference's parameters (it needs the optional pydensecrf package);
+`do_crf(..., backend="device")` runs the exact mean-field inference of the same model on the GPU (crf.py, csrc/crf.hip).
 The cv2 augmentation chain (utils.py:319-365) runs on the device (augment.py, dl3_augment) behind
 SegmentationGenerator's augmentation keywords and SegModel.create_generators.
 Out of scope by the SURVEY §8 contract: image file I/O, plotting.
@@ -102,8 +103,8 @@ def prepare_targets(labels, n_classes=21):
     return Y, SW
 
 
-# Dense-CRF post-processing stays on the host (north star): the hook and the reference's parameter set
-# (utils.py:74-91).  pydensecrf is not a dependency of this package: the hook imports it on first use.
+# Dense-CRF post-processing: the reference's parameter set (utils.py:74-91), shared by the host hook and
+# the device backend.  pydensecrf is not a dependency of this package: the hook imports it on first use.
 CRF_PARAMS = dict(gt_prob=0.7, gaussian_sxy=(3, 3), gaussian_compat=3, bilateral_sxy=80, bilateral_srgb=13,
                   bilateral_compat=10, iterations=5)
 
@@ -119,11 +120,25 @@ def restore_crf_labels(MAP, colors):
     return MAP
 
 
-def do_crf(im, mask, zero_unsure=True):
+def do_crf(im, mask, zero_unsure=True, backend="pydensecrf"):
     """Fully connected CRF refinement of a label mask given the image (reference utils.py:74-91): unary energies from
     the labels with CRF_PARAMS['gt_prob'], a Gaussian (position) and a bilateral (position + colour) pairwise term,
     five mean-field iterations, MAP labels mapped back to the mask's original values by the reference's own in-place
-    loop (restore_crf_labels)."""
+    loop (restore_crf_labels).
+
+    backend="pydensecrf" (the default) is the reference's call sequence on the host and needs that package;
+    backend="device" runs the exact mean-field inference of the same model on the GPU (crf.dense_crf, dl3_crf_inference:
+    all pixel pairs instead of pydensecrf's lattice approximation) and returns the same type and shape.
+    A mask with a single value is returned unchanged by the device backend (pydensecrf's unary divides by
+    n_labels - 1)."""
+    if backend == "device":
+        from .crf import dense_crf
+        mask = np.asarray(mask)
+        if len(np.unique(mask)) < 2:
+            return mask
+        return dense_crf(np.asarray(im)[None], mask.reshape((1,) + mask.shape[:2]), zero_unsure=zero_unsure)[0]
+    if backend != "pydensecrf":
+        raise ValueError("do_crf: backend must be 'pydensecrf' or 'device', got %r" % (backend,))
     try:
         import pydensecrf.densecrf as dcrf
         from pydensecrf.utils import unary_from_labels

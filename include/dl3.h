@@ -397,6 +397,40 @@ int dl3_prepare_targets(const void *labels, int label_dtype, int B, int HW, int 
  * (utils.Jaccard_from_counts): union = true + pred - inter, exactly the reference's inter/union sums. */
 int dl3_seg_counts(const int *pred, const float *y_true, int B, int HW, int C, int *counts, void *stream);
 
+/* ---- evaluation tail (Model.evaluate / validation): loss sums, metric counts, confusion matrix and the
+ * argmax mask from the LOW-resolution logits and the labels in one pass — neither full-resolution logits nor
+ * probabilities are written.  Three input forms:
+ *   bilinear  logits_lo [N][Hi][Wi][C], labels / weights [N][Ho][Wo]: the TF1 legacy bilinear resize applied in registers,
+ *             bit-identical to dl3_resize_bilinear_fwd (so the mask equals dl3_resize_bilinear_fwd + dl3_argmax); the loss
+ *             interpolates with TF's stated weight fl(o * scale) - lo (the resize kernel fuses that into one fma);
+ *   shuffle   u [N][H][W][C*r*r] (the Subpixel convolution's output), labels / weights [N][H*r][W*r]: dl3_phase_shift by index;
+ *   plain     materialised logits [N*HW][C], C <= 255.
+ * The fused forms need C <= 32; their *_partials query returns 0 for a shape they do not support (fall back to
+ * dl3_resize_bilinear_fwd / dl3_phase_shift followed by the plain form).  labels: float, void = C (as fed to the loss);
+ * weights nullable (w = 1).  Outputs, per call:
+ *   loss_sum[N]   (double) per image sum_m w[m] * l[m], l the per-pixel expression of dl3_softmax_xent (softmax, Keras'
+ *                 renormalise, clip to [1e-7, 1-1e-7], void -> 0), the fp32 terms added in double: per-workgroup partials[N][P] (double),
+ *                 P = dl3_eval_tail_*_partials(...), folded per image in a fixed order in double by a second launch — no
+ *                 float atomics, two runs are bit-identical;
+ *   nnz[N]        (int32) count(w != 0) per image;
+ *   counts[N][3][C] (int32) exactly dl3_seg_counts' contract;
+ *   confusion[C][C] (int64, nullable) += #(label == row && prediction == column), void labels skipped: it ACCUMULATES
+ *                 across calls (a whole validation pass needs no host trip); the caller zeroes it;
+ *   mask[N][Ho][Wo] (int32, nullable) argmax, first maximum wins like dl3_argmax.
+ * Integer outputs go through a per-workgroup LDS histogram and one global integer atomic per non-zero bin: exact and
+ * independent of arrival order. */
+int dl3_eval_tail_bilinear_partials(int N, int Hi, int Wi, int Ho, int Wo, int C);
+int dl3_eval_tail_bilinear(const float *logits_lo, const float *labels, const float *weights, double *partials,
+                           double *loss_sum, int *nnz, int *counts, long long *confusion, int *mask, int N, int Hi, int Wi,
+                           int Ho, int Wo, int C, void *stream);
+int dl3_eval_tail_shuffle_partials(int N, int H, int W, int C, int r);
+int dl3_eval_tail_shuffle(const float *u, const float *labels, const float *weights, double *partials, double *loss_sum,
+                          int *nnz, int *counts, long long *confusion, int *mask, int N, int H, int W, int C, int r,
+                          void *stream);
+int dl3_eval_tail_plain_partials(int N, int HW, int C);
+int dl3_eval_tail_plain(const float *logits, const float *labels, const float *weights, double *partials, double *loss_sum,
+                        int *nnz, int *counts, long long *confusion, int *mask, int N, int HW, int C, void *stream);
+
 /* ---- training augmentation (SegmentationGenerator.__getitem__, utils.py:310-369) ------------------------------------
  * images[B][Hs][Ws][3] uint8 (BGR) and labels[B][Hs][Ws] (label_dtype) -> X[B][H][W][3] float32 (the engine's input) and
  * labels_out[B][H][W] (label_dtype; with DL3_AUG_WARP uint8, values the interpolation created set to C = void).

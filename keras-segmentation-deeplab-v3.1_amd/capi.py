@@ -28,6 +28,8 @@ _CTYPES = {
     "const unsigned char *": ctypes.c_void_p,
     "void * *": ctypes.POINTER(ctypes.c_void_p),
     "const long long *": ctypes.c_void_p,
+    "long long *": ctypes.c_void_p,
+    "double *": ctypes.c_void_p,
     "unsigned long long *": ctypes.c_void_p,
     "const unsigned long long *": ctypes.c_void_p,
     "const char *": ctypes.c_char_p,

@@ -1206,17 +1206,22 @@ class Engine:
         out = out.reshape(self.B, v.buf.H, v.buf.W)
         return out.cpu().numpy() if host else out
 
-    def set_targets(self, y, sw=None):
+    def set_targets(self, y, sw=None, fill_weights=True):
         """labels [B,HW,1] (void = classes) and temporal sample weights [B,HW]; numpy arrays or device tensors (e.g. the
-        output of utils.prepare_targets, which then never leaves the GPU)"""
+        output of utils.prepare_targets, which then never leaves the GPU).  On an inference engine the buffers belong to
+        the evaluation plan (evaluate_batch), whose tail takes `no weights` as a NULL pointer (fill_weights=False)."""
         M = self.logits_view.buf.M
+        if not self.training:
+            self._eval_setup()
         if torch.is_tensor(y):
             yt = y.reshape(-1).to(torch.float32)
         else:
             yt = torch.from_numpy(np.ascontiguousarray(np.asarray(y, np.float32).reshape(-1)))
         assert yt.numel() == M, (yt.numel(), M)
         self.labels.copy_(yt.to(self.device, non_blocking=True))
-        if sw is None:
+        if sw is None and not fill_weights:
+            pass
+        elif sw is None:
             # Keras without sample weights: plain mean over all B*HW pixels; void rows contribute zero loss and zero
             # gradient through the one-hot (utils.py:129), not through a weight
             capi.call("dl3_fill", ptr(self.sweights), 1.0, M, torch.cuda.current_stream().cuda_stream)
@@ -1270,6 +1275,134 @@ class Engine:
         counts = torch.empty(self.B, 3, v.C, dtype=torch.int32, device=self.device)
         capi.call("dl3_seg_counts", pred.data_ptr(), yt.data_ptr(), self.B, v.buf.M // self.B, v.C, counts.data_ptr(), st)
         return counts.cpu().numpy()
+
+    # ------------------------------------------------------------------ evaluation plan
+    def _eval_setup(self):
+        """the evaluation plan of an inference engine: the forward op list minus the final resize / phase-shift launch
+        (`ops_fwd` itself stays as it is: predict / logits() / argmax() keep using it) plus the evaluation tail
+        (dl3_eval_tail_*), which turns the low-resolution logits and the labels into loss sums, counts, confusion matrix
+        and mask — neither full-resolution logits nor probabilities are written.  Any other graph (and C > 32) keeps its
+        whole forward plan and ends in the plain form on the materialised logits."""
+        ev = getattr(self, "_eval", None)
+        if ev is not None:
+            return ev
+        if self.training:
+            raise RuntimeError("Engine.evaluate_batch needs an inference engine (training=False)")
+        v = self.logits_view
+        M, C, B, lib = v.buf.M, v.C, self.B, self.lib
+        ops = list(self.ops_fwd)
+        last = self.units[-1] if self.units else None
+        form = None
+        if last is not None and last.outv.buf is v.buf and ops and not last.inv.aff and last.inv.act == ACT_NONE \
+                and last.inv.off == 0:
+            if isinstance(last, ResizeUnit) and ops[-1][0] == "dl3_resize_bilinear_fwd" and last.inv.ld == C:
+                _, Hi, Wi, Ho, Wo, _ = last.dims
+                P = lib.dl3_eval_tail_bilinear_partials(B, Hi, Wi, Ho, Wo, C)
+                if P > 0:
+                    form, src, dims = "bilinear", last.inv.p(), (B, Hi, Wi, Ho, Wo, C)
+            elif isinstance(last, ShuffleUnit) and ops[-1][0] == "dl3_phase_shift" \
+                    and last.inv.ld == last.co * last.r * last.r and last.co == C:
+                P = lib.dl3_eval_tail_shuffle_partials(B, last.inv.buf.H, last.inv.buf.W, C, last.r)
+                if P > 0:
+                    form, src, dims = "shuffle", last.inv.p(), (B, last.inv.buf.H, last.inv.buf.W, C, last.r)
+        if form is None:
+            P = lib.dl3_eval_tail_plain_partials(B, M // B, C)
+            if P <= 0:
+                raise capi.DL3Error("dl3_eval_tail_plain does not support %d classes" % C)
+            form, src, dims = "plain", ptr(v.buf.t), (B, M // B, C)
+        else:
+            ops.pop()
+        # labels / weights of the batch (set_targets), the tail's own buffers and ONE record of its results:
+        # loss_sum double[B] | nnz int32[B] | counts int32[B][3][C]
+        self.labels = self.zeros(M)
+        self.sweights = self.zeros(M)
+        rec_bytes = (8 * B + 4 * B + 4 * B * 3 * C + 15) // 16 * 16
+        ev = dict(form=form, src=src, dims=dims, ops=ops, plans={}, n=0, rec_bytes=rec_bytes,
+                  part=self.empty(2 * B * P), mask=torch.empty(M, dtype=torch.int32, device=self.device),
+                  rec=torch.zeros(rec_bytes, dtype=torch.uint8, device=self.device),
+                  results=torch.zeros(8, rec_bytes, dtype=torch.uint8, device=self.device))
+        self._eval = ev
+        return ev
+
+    def eval_op_names(self, confusion=None, mask=False):
+        """the launch names of the evaluation plan (tests: no final resize / phase shift / softmax in it)"""
+        return [rec[0] for rec in self._eval_plan(confusion, True, mask)["ops"]]
+
+    def _eval_plan(self, confusion, weighted, mask):
+        ev = self._eval_setup()
+        key = (0 if confusion is None else confusion.data_ptr(), bool(weighted), bool(mask))
+        plan = ev["plans"].get(key)
+        if plan is None:
+            B, C = self.B, self.logits_view.C
+            if confusion is not None and (confusion.dtype != torch.int64 or confusion.numel() != C * C
+                                          or not confusion.is_contiguous() or confusion.device != self.device):
+                raise ValueError("confusion must be a contiguous int64 [%d,%d] tensor on %s" % (C, C, self.device))
+            base = ev["rec"].data_ptr()
+            args = [ev["src"], ptr(self.labels), ptr(self.sweights) if weighted else None, ptr(ev["part"]), base,
+                    base + 8 * B, base + 12 * B, None if confusion is None else confusion.data_ptr(),
+                    ev["mask"].data_ptr() if mask else None] + list(ev["dims"])
+            name = "dl3_eval_tail_" + ev["form"]
+            plan = dict(ops=ev["ops"] + [(name, getattr(self.lib, name), args, None)], calls=0, graph=None,
+                        confusion=confusion)
+            ev["plans"][key] = plan
+        return plan
+
+    def evaluate_batch(self, x, y, sw=None, confusion=None, mask=False):
+        """forward + evaluation tail on (x, y, sw), everything on the device: the batch's loss sums, count(w != 0) and
+        dl3_seg_counts' counts land in the next record of a device buffer that `read_evaluation()` fetches ONCE per pass.
+        confusion: a contiguous int64 [C,C] device tensor the batch is ADDED to (the caller zeroes it); mask=True returns
+        the int32 masks [B,H,W] as a device tensor (valid until the next call).  Each (confusion, weighted, mask) variant
+        is replayed as a hipGraph of its own from its second call on.
+        The host waits for the stream to drain before it enqueues (the trap recorded in train_step: a graph replay
+        behind a pageable device-to-host copy)."""
+        plan = self._eval_plan(confusion, sw is not None, mask)
+        ev = self._eval
+        torch.cuda.current_stream().synchronize()
+        self.set_input(x)
+        self.set_targets(y, sw, fill_weights=False)
+        self._prep()
+        if self.use_graph and plan["calls"] >= 1:
+            if plan["graph"] is None:
+                torch.cuda.synchronize()
+                try:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self.run_ops(plan["ops"])
+                    plan["graph"] = g
+                except Exception as e:  # pragma: no cover - depends on the runtime
+                    print("dl3: hipGraph capture failed (%s); running eagerly" % e)
+                    self.use_graph = False
+                    torch.cuda.synchronize()
+            if plan["graph"] is not None:
+                plan["graph"].replay()
+            else:
+                self.run_ops(plan["ops"])
+        else:
+            self.run_ops(plan["ops"])
+        plan["calls"] += 1
+        if ev["n"] == ev["results"].shape[0]:
+            grown = torch.zeros(2 * ev["n"], ev["rec_bytes"], dtype=torch.uint8, device=self.device)
+            grown[:ev["n"]].copy_(ev["results"])
+            ev["results"] = grown
+        ev["results"][ev["n"]].copy_(ev["rec"])
+        ev["n"] += 1
+        if mask:
+            v = self.logits_view
+            return ev["mask"].reshape(self.B, v.buf.H, v.buf.W)
+        return None
+
+    def read_evaluation(self):
+        """the records written since the last read, in ONE device-to-host copy behind a host-side stream synchronisation:
+        (loss_sum [n,B] float64, nnz [n,B] int32, counts [n,B,3,C] int32); the record counter starts over"""
+        ev = self._eval_setup()
+        n, B, C = ev["n"], self.B, self.logits_view.C
+        torch.cuda.current_stream().synchronize()
+        raw = ev["results"][:n].cpu().numpy() if n else np.zeros((0, ev["rec_bytes"]), np.uint8)
+        ev["n"] = 0
+        loss = np.ascontiguousarray(raw[:, :8 * B]).view(np.float64).reshape(n, B)
+        nnz = np.ascontiguousarray(raw[:, 8 * B:12 * B]).view(np.int32).reshape(n, B)
+        counts = np.ascontiguousarray(raw[:, 12 * B:12 * B + 12 * B * C]).view(np.int32).reshape(n, B, 3, C)
+        return loss, nnz, counts
 
     def fwd_bwd(self):
         """forward + loss + backward on the resident batch (the benchmarked hot path)"""

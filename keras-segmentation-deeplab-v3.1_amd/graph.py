@@ -598,11 +598,17 @@ class Model:
                 outs.append(eng.argmax())
         return np.concatenate(outs, axis=0)
 
-    def evaluate(self, x, y, batch_size=32, sample_weight=None, verbose=0):
+    def evaluate(self, x, y, batch_size=32, sample_weight=None, verbose=0, device=False):
         """keras Model.evaluate for the notebook's metrics (cell 2: metrics=[Jaccard, sparse_accuracy_ignoring_last_label]):
         returns [loss, Jaccard, accuracy].  The argmax mask and the per-image/per-class pixel counts are produced on
         the device (dl3_argmax, dl3_seg_counts); the metric ratios (utils.py:132-157) and the loss (utils.py:127-130,
-        Keras weighted mean) are evaluated on the host from those counts / the probabilities."""
+        Keras weighted mean) are evaluated on the host from those counts / the probabilities.
+        device=True: the evaluation plan (Engine.evaluate_batch) — nothing but a small result buffer
+        crosses PCIe, once per call — with Keras 2.2.4's averaging [TF-semantics, from memory]: every number is formed per
+        BATCH and the call returns the average over batches weighted by batch size.  (The host path pools the counts of
+        all batches before it forms the metric ratios; it stays as it is.)"""
+        if device:
+            return self._evaluate_device(self._xy_batches(x, y, sample_weight, batch_size))[0]
         from . import utils as U
         if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
             x = np.asarray(x, np.float32)
@@ -627,6 +633,136 @@ class Model:
             den += xb.shape[0]
         counts = np.concatenate(counts, 0)
         return [num / den, U.Jaccard_from_counts(counts), U.accuracy_from_counts(counts)]
+
+    # -- evaluation on the device ------------------------------------------------------------------
+    @staticmethod
+    def _xy_batches(x, y, sample_weight, batch_size):
+        if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
+            x = np.asarray(x, np.float32)
+        n = x.shape[0]
+        bs = min(int(batch_size), n)
+        for i in range(0, n, bs):
+            yield x[i:i + bs], y[i:i + bs], (None if sample_weight is None else sample_weight[i:i + bs])
+
+    @staticmethod
+    def _generator_batches(generator, steps=None):
+        """(X, Y, SW) of a generator's items: (X, Y), (X, Y, SW) or (X, Y, {'pred_mask': SW})"""
+        steps = len(generator) if steps is None else int(steps)
+        for i in range(steps):
+            item = generator[i] if hasattr(generator, "__getitem__") else next(generator)
+            SW = item[2] if len(item) > 2 else None
+            if isinstance(SW, dict):
+                SW = list(SW.values())[0]
+            yield item[0], item[1], SW
+
+    def _evaluate_device(self, batches, confusion=None):
+        """one evaluation pass: every batch through Engine.evaluate_batch, the results of the whole pass read once per
+        engine (a ragged last batch has an engine of its own).  -> ([loss, Jaccard, accuracy] averaged over the batches
+        weighted by batch size, the per-batch triples, the batch sizes)"""
+        from . import utils as U
+        used, fresh = [], set()
+        for xb, yb, swb in batches:
+            eng = self._engine(xb.shape[0], False)
+            if id(eng) not in fresh:
+                fresh.add(id(eng))
+                eng._eval_setup()["n"] = 0
+            eng.evaluate_batch(xb, yb, swb, confusion=confusion)
+            used.append(eng)
+        if not used:
+            raise ValueError("evaluation over zero batches")
+        read, per, sizes = {}, [], []
+        for eng in used:
+            if id(eng) not in read:
+                read[id(eng)] = [eng.read_evaluation(), 0]
+            (loss, nnz, counts), k = read[id(eng)]
+            read[id(eng)][1] += 1
+            n = int(nnz[k].sum())
+            # sum(l*w) / count(w != 0) of the batch; no weight non-zero: every term is zero (no division)
+            per.append([float(loss[k].sum() / n) if n else 0.0, U.Jaccard_from_counts(counts[k]),
+                        U.accuracy_from_counts(counts[k])])
+            sizes.append(eng.B)
+        a, w = np.asarray(per, np.float64), np.asarray(sizes, np.float64)
+        return [float(v) for v in (a * w[:, None]).sum(0) / w.sum()], per, sizes
+
+    def evaluate_generator(self, generator, steps=None, **kw):
+        """keras Model.evaluate_generator on the device: [loss, Jaccard, sparse_accuracy_ignoring_last_label], per-batch
+        values averaged with the batch sizes as weights (Keras 2.2.4 [TF-semantics, from memory])"""
+        self._check_fit_kw(kw)
+        return self._evaluate_device(self._generator_batches(generator, steps))[0]
+
+    def confusion_matrix(self, x_or_generator, y=None, batch_size=32):
+        """int64 [C,C], row = label, column = prediction, void labels skipped — the notebook's calculate_iou loop (cell 10)
+        as one device pass: the matrix accumulates on the device across batches and crosses PCIe once"""
+        import torch
+        C = int(self.output.shape[-1])
+        buf = getattr(self, "_confusion_buf", None)
+        if buf is None or buf.shape[0] != C:
+            buf = self._confusion_buf = torch.zeros(C, C, dtype=torch.int64, device="cuda")
+        buf.zero_()
+        batches = self._generator_batches(x_or_generator) if y is None else self._xy_batches(x_or_generator, y, None, batch_size)
+        self._evaluate_device(batches, confusion=buf)
+        return buf.cpu().numpy()
+
+    _KNOWN_METRICS = ("Jaccard", "sparse_accuracy_ignoring_last_label")
+
+    def _metric_names(self):
+        """names of compile(metrics=...) — a list or {'pred_mask': [...]} of the two metrics this package knows"""
+        m = (self._compiled or {}).get("metrics") or []
+        if isinstance(m, dict):
+            m = [f for v in m.values() for f in (v if isinstance(v, (list, tuple)) else [v])]
+        names = []
+        for f in m:
+            name = f if isinstance(f, str) else getattr(f, "__name__", None)
+            if name not in self._KNOWN_METRICS:
+                raise ValueError("validation: metric %r is not one of %s (the metrics the evaluation tail produces)"
+                                 % (f, list(self._KNOWN_METRICS)))
+            names.append(name)
+        return names
+
+    def _validator(self, validation_data, validation_steps, batch_size):
+        """() -> {'val_loss': .., 'val_<metric>': ..} for fit / fit_generator.  Under distribute() every rank evaluates
+        the whole validation set on its own replica: identical weights give identical logs and identical callback
+        decisions without a collective."""
+        if validation_data is None:
+            return None
+
+        def validate():
+            names = self._metric_names()
+            if isinstance(validation_data, (tuple, list)):
+                sw = validation_data[2] if len(validation_data) > 2 else None
+                batches = self._xy_batches(validation_data[0], validation_data[1], sw, batch_size)
+            else:
+                batches = self._generator_batches(validation_data, validation_steps)
+            vals = self._evaluate_device(batches)[0]
+            logs = {"val_loss": vals[0]}
+            for name in names:
+                logs["val_" + name] = vals[1 + self._KNOWN_METRICS.index(name)]
+            return logs
+        return validate
+
+    def _get_lr(self):
+        opt = (self._compiled or {}).get("optimizer") or {}
+        return float(opt.get("lr", 7e-4))   # Engine.adam's default: the notebook's Adam(lr=7e-4)
+
+    def _set_lr(self, lr):
+        """a new learning rate from the next step on: the compiled hyper-parameter dict (Engine.adam takes it per call —
+        no new engine, Adam's moments and iteration untouched) and the optimizer object's `lr` if there is one"""
+        if self._compiled is None:
+            self._compiled = dict(optimizer={}, optimizer_object=None, loss=None, metrics=None, sample_weight_mode=None)
+        self._compiled["optimizer"]["lr"] = float(lr)
+        obj = self._compiled.get("optimizer_object")
+        if obj is not None and not isinstance(obj, (dict, str)) and hasattr(obj, "lr"):
+            obj.lr = float(lr)
+
+    def _fit_session(self, kw, epochs, steps, batch_size):
+        """takes callbacks= / validation_data= / validation_steps= out of kw; None when neither callbacks nor validation
+        were asked for (fit then returns its plain list of losses, as before)"""
+        callbacks = kw.pop("callbacks", None)
+        validation_data = kw.pop("validation_data", None)
+        validation_steps = kw.pop("validation_steps", None)
+        if not callbacks and validation_data is None:
+            return None
+        return _FitSession(self, callbacks, self._validator(validation_data, validation_steps, batch_size), epochs, steps)
 
     def _dp_active(self):
         dp = self._dp
@@ -678,21 +814,29 @@ class Model:
         for k, v in kw.items():
             if k in self._IGNORED_FIT_KW or v is None or (isinstance(v, (list, tuple)) and not v):
                 continue
-            warnings.warn("dl3: Model.fit/fit_generator does not implement %r (the training loop of the reference, "
-                          "utils.py:216-254, is host-side control plane outside this package): it is IGNORED — drive "
-                          "callbacks / validation from your own loop around train_on_batch / evaluate" % k,
+            warnings.warn("dl3: Model.fit/fit_generator does not implement %r: it is IGNORED" % k,
                           RuntimeWarning, stacklevel=3)
 
     def fit(self, x, y, batch_size=16, epochs=1, sample_weight=None, verbose=0, **kw):
-        """Minimal Model.fit (utils.py:244): plain epochs over (x, y) without shuffling or callbacks."""
+        """Minimal Model.fit (utils.py:244): plain epochs over (x, y) without shuffling.
+        validation_data=(x, y[, sw]) and / or callbacks=[...] (callbacks.py): after every epoch the validation set goes
+        through the evaluation plan on the device and the callbacks see {'loss', 'val_loss', 'val_<metric>'...}; the call
+        then returns a callbacks.History instead of the list of losses."""
+        n = x.shape[0]
+        ses = self._fit_session(kw, epochs, max(n // batch_size, 0), batch_size)
         self._check_fit_kw(kw)
         hist = []
-        n = x.shape[0]
-        for _ in range(epochs):
-            for i in range(0, n - batch_size + 1, batch_size):
+        for ep in range(epochs):
+            if ses:
+                ses.epoch_begin(ep)
+            for b, i in enumerate(range(0, n - batch_size + 1, batch_size)):
                 sw = None if sample_weight is None else sample_weight[i:i + batch_size]
                 hist.append(self.train_on_batch(x[i:i + batch_size], y[i:i + batch_size], sw, lazy_loss=True))
-        return [float(l) for l in hist]
+                if ses:
+                    ses.batch_end(b, batch_size, hist[-1])
+            if ses and ses.epoch_end(ep):
+                break
+        return ses.end() if ses else [float(l) for l in hist]
 
     def fit_generator(self, generator, steps_per_epoch=None, epochs=1, verbose=0, device_feed=False, n_classes=None,
                       global_batch=True, **kw):
@@ -702,15 +846,20 @@ class Model:
         batch crosses PCIe as bytes on a copy stream while the previous step runs, and X / Y / SW are produced on the device
         (feed.BatchFeeder: widening copy + dl3_prepare_targets).  A utils.SegmentationGenerator is read through its
         raw_batch(i): with augmentation on, the feeder runs dl3_augment on the device instead of the widening copy.
+        validation_data=generator | (x, y[, sw]), validation_steps=, callbacks=[...]: as in fit(); validation batches come
+        from the generator's __getitem__ (also with device_feed=True: the feed serves the training half).
         Under distribute() (utils.py:209-211 + :231-241): global_batch=True — the generator yields the GLOBAL batch and each
         rank stages only its contiguous shard (rows dp.shard(n)) — or global_batch=False — the generator is already sharded
         by rank (e.g. `idx[rank::world]`) and yields this rank's images only.  Either way only the shard crosses PCIe."""
+        steps = steps_per_epoch or len(generator)
+        ses = self._fit_session(kw, epochs, steps, getattr(generator, "batch_size", 32))
         self._check_fit_kw(kw)
         hist = []
-        steps = steps_per_epoch or len(generator)
         if device_feed:
-            return self._fit_device_feed(generator, steps, epochs, n_classes, global_batch)
-        for _ in range(epochs):
+            return self._fit_device_feed(generator, steps, epochs, n_classes, global_batch, ses)
+        for ep in range(epochs):
+            if ses:
+                ses.epoch_begin(ep)
             for i in range(steps):
                 item = generator[i] if hasattr(generator, "__getitem__") else next(generator)
                 X, Y = item[0], item[1]
@@ -718,22 +867,30 @@ class Model:
                 if isinstance(SW, dict):
                     SW = list(SW.values())[0]
                 hist.append(self.train_on_batch(X, Y, SW, lazy_loss=True, global_batch=global_batch))
+                if ses:
+                    ses.batch_end(i, X.shape[0], hist[-1])
             hist = [float(l) for l in hist]   # one read per epoch
+            if ses and ses.epoch_end(ep):
+                break
             if hasattr(generator, "on_epoch_end"):
                 generator.on_epoch_end()
-        return hist
+        return ses.end() if ses else hist
 
-    def _fit_device_feed(self, generator, steps, epochs, n_classes, global_batch=True):
+    def _fit_device_feed(self, generator, steps, epochs, n_classes, global_batch=True, ses=None):
         from .feed import BatchFeeder
         dp = self._dp if self._dp_active() else None
         ekw = dict(external_nnz=True) if dp is not None else {}
-        opt = (self._compiled or {}).get("optimizer") or {}
         C = int(n_classes if n_classes is not None else self.output.shape[-1])
         hist, feeders = [], {}
         # utils.SegmentationGenerator: raw_batch() gives the source bytes (+ augmentation parameters) of a batch
         raw = hasattr(generator, "raw_batch")
         plan = getattr(generator, "plan", None) if raw else None
-        for _ in range(epochs):
+        for ep in range(epochs):
+            # read every epoch: a callback (ReduceLROnPlateau) may have changed the learning rate
+            opt = (self._compiled or {}).get("optimizer") or {}
+            if ses:
+                ses.epoch_begin(ep)
+
             def batches():
                 for i in range(steps):
                     if raw:
@@ -779,9 +936,54 @@ class Model:
                     dp.allreduce_grads(eng.grads)
                 eng.adam(opt)   # (norm defaults to the engine's external_nnz)
                 losses.append(eng.loss_handle())
+                if ses:
+                    ses.batch_end(len(losses) - 1, eng.B, losses[-1])
 
             feeders[key].run(chain(), step)
             hist += [float(l) for l in losses]   # one read per epoch
+            if ses and ses.epoch_end(ep):
+                break
             if hasattr(generator, "on_epoch_end"):
                 generator.on_epoch_end()
-        return hist
+        return ses.end() if ses else hist
+
+
+class _FitSession:
+    """callbacks and validation around the epochs of fit / fit_generator (the loop of keras.engine.training_generator):
+    on_train_begin | per epoch: on_epoch_begin, on_batch_end per step (logs['loss'] is the step's LazyLoss — nothing is
+    read unless a callback converts it), then ONE read of the epoch's losses, the validation pass, on_epoch_end with
+    {'loss', 'val_*'} | on_train_end.  Training-batch Jaccard / accuracy are not produced (the fused training tails never
+    form a mask)."""
+
+    def __init__(self, model, callbacks, validate, epochs, steps):
+        from .callbacks import CallbackList, History
+        self.model, self.validate = model, validate
+        self.history = History()
+        self.cbs = CallbackList(list(callbacks or []) + [self.history])   # History last: it records what the others add
+        self.cbs.set_model(model)
+        self.cbs.set_params(dict(epochs=epochs, steps=steps, verbose=0, do_validation=validate is not None))
+        model.stop_training = False
+        self.cbs.on_train_begin()
+
+    def epoch_begin(self, epoch):
+        self.losses, self.sizes = [], []
+        self.cbs.on_epoch_begin(epoch)
+
+    def batch_end(self, batch, size, loss):
+        self.losses.append(loss)
+        self.sizes.append(int(size))
+        self.cbs.on_batch_end(batch, dict(batch=batch, size=int(size), loss=loss))
+
+    def epoch_end(self, epoch):
+        """-> True when a callback asked to stop"""
+        vals = np.asarray([float(l) for l in self.losses], np.float64)   # the epoch's one read
+        w = np.asarray(self.sizes, np.float64)
+        logs = {"loss": float((vals * w).sum() / w.sum()) if len(vals) else float("nan")}
+        if self.validate is not None:
+            logs.update(self.validate())
+        self.cbs.on_epoch_end(epoch, logs)
+        return bool(self.model.stop_training)
+
+    def end(self):
+        self.cbs.on_train_end()
+        return self.history

@@ -17,6 +17,9 @@ from . import graph as G
 from .deeplabv3p import Deeplabv3
 from .graph import Activation, Conv2D, Model, Reshape, ResizeBilinear
 from .subpixel import Subpixel, icnr_weights
+# the reference's `from utils import *` hands the notebook Keras' callbacks (utils.py: `from keras.callbacks import *`)
+from .callbacks import (Callback, EarlyStopping, History, LambdaCallback, ModelCheckpoint,  # noqa: F401
+                        ReduceLROnPlateau)
 
 
 def sparse_crossentropy_ignoring_last_label(y_true, y_pred):
@@ -79,6 +82,18 @@ def accuracy_from_counts(counts):
     """`sparse_accuracy_ignoring_last_label` (utils.py:132-138) from dl3_seg_counts output."""
     counts = np.asarray(counts, np.int64)
     return float(counts[:, 2].sum() / max(counts[:, 0].sum(), 1))
+
+
+def calculate_iou(model, X, label, nb_classes=21):
+    """segmentation.ipynb cell 10 on the device: the notebook walks every pixel in Python and fills
+    `conf_m[l - 1, p - 1] += 1` for labels below 255; here Model.confusion_matrix accumulates the matrix in one device
+    pass.  Returned in the notebook's own layout, as float: index -1 wraps, so class 0 lands in the LAST row / column
+    (np.roll(plain, -1, axis=(0, 1))) — reproduced, not fixed.  X [N,H,W,3] raw 0-255 images, label [N,H,W] with void
+    >= nb_classes (255 in VOC)."""
+    label = np.asarray(label)
+    y = np.where((label >= 0) & (label < nb_classes), label, nb_classes).astype(np.float32).reshape(len(label), -1, 1)
+    plain = np.asarray(model.confusion_matrix(X, y))
+    return np.roll(plain, -1, axis=(0, 1)).astype(float)
 
 
 def prepare_targets(labels, n_classes=21):
@@ -251,7 +266,7 @@ class SegmentationGenerator:
 
 
 class SegModel:
-    """utils.py:160-254 — only model construction is on the path."""
+    """utils.py:160-254 — model construction, the generators and train_generator."""
     epochs = 20
     batch_size = 16
 
@@ -330,6 +345,15 @@ class SegModel:
 
     def load_weights(self, model):
         model.load_weights(self.modelpath)
+
+    def train_generator(self, model, train_generator, valid_generator, callbacks, mp=True, workers=1, max_queue_size=10):
+        """utils.py:231-241: one fit_generator call over the two generators with the notebook's callbacks; returns the
+        History.  mp / workers / max_queue_size are accepted and ignored (batches are produced on the device).
+        `SegModel.train` is not built: as committed it calls a `self.build_callbacks` the class does not have."""
+        return model.fit_generator(train_generator, steps_per_epoch=len(train_generator), epochs=self.epochs, verbose=1,
+                                   callbacks=callbacks, validation_data=valid_generator,
+                                   validation_steps=len(valid_generator), max_queue_size=max_queue_size,
+                                   workers=workers, use_multiprocessing=mp)
 
     @classmethod
     def set_num_epochs(cls, new_epochs):

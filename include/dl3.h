@@ -469,6 +469,29 @@ int dl3_crf_message(const float *feat, int D, const float *Qin, int B, int N, in
 int dl3_crf_inference(const unsigned char *im, const float *U, int B, int H, int W, int L, const float *params,
                       int iters, float *Q, float *energy, int *map, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- the dense CRF's unary energies from the network's class scores ("softmax unary") ----------------
+ * pydensecrf.utils.unary_from_softmax(sm, scale=None, clip=1e-5) [pydensecrf-semantics] on the device, per pixel:
+ *   p = softmax(scores) over the classes (plain form with is_prob = 1: p = x as given);
+ *   scale > 0: p = scale * p + (1 - scale) / C   (scale <= 0 stands for None);
+ *   clip  > 0: p = min(max(p, clip), 1)          (clip <= 0 stands for None);
+ *   U = -log p, written as the planar U[B][C][N] that dl3_crf_inference reads (the MAP index is then the class id).
+ * Three input forms, the ones of dl3_eval_tail_*:
+ *   plain     x [B][N][C]: materialised logits, or probabilities (is_prob = 1);
+ *   bilinear  logits_lo [B][Hi][Wi][C], N = Ho * Wo: the TF1 legacy bilinear resize applied in registers, the interpolated
+ *             logits bit-identical to dl3_resize_bilinear_fwd;
+ *   shuffle   u [B][H][W][C*r*r] (the Subpixel convolution's output), N = H*r * W*r: dl3_phase_shift by index.
+ * scale and clip cross this boundary as floats: a value that float cannot hold exactly (0.3, 1e-5) is applied as its
+ * float rounding, a relative difference of up to 6e-8 in the mixing weight or the clip level from the same number held
+ * as a double.  scale > 1 (the uniform part would turn negative) and clip >= 1 (every energy would be 0) are refused (-1).
+ * C <= 32, the limit of dl3_crf_inference (-4 above).  subtract-max, expf and the sum in fp32; quotient, scale, clip and
+ * logarithm in double, rounded once.  No atomics: two runs are bit-identical.  The arg-min of U over the classes is the
+ * first-maximum argmax of the scores (dl3_argmax) wherever it is unique. */
+int dl3_crf_unary_plain(const float *x, int is_prob, float *U, int B, int N, int C, float scale, float clip, void *stream);
+int dl3_crf_unary_bilinear(const float *logits_lo, float *U, int B, int Hi, int Wi, int Ho, int Wo, int C, float scale,
+                           float clip, void *stream);
+int dl3_crf_unary_shuffle(const float *u, float *U, int B, int H, int W, int C, int r, float scale, float clip,
+                          void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

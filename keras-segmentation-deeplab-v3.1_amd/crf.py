@@ -4,7 +4,11 @@ position + colour kernel, symmetric normalisation, Potts compatibility, parallel
 dl3_crf_inference (csrc/crf.hip) instead of pydensecrf's permutohedral lattice [pydensecrf-semantics].
 Results agree with pydensecrf only as far as its lattice approximates these sums.
 
-The unary energies are built on the host in numpy (O(N L)); every parameter comes from utils.CRF_PARAMS.
+The label unary energies are built on the host in numpy (O(N L)); every parameter comes from utils.CRF_PARAMS.
+
+dense_crf_softmax takes the network's own class scores instead of a label mask: the unary energies are
+unary_from_softmax of the probabilities, formed on the device (dl3_crf_unary_*, csrc/crfunary.hip) with one label per
+class, so the MAP index IS the class id — no np.unique, no host unary, no padding energy, no restore table.
 """
 import numpy as np
 
@@ -111,3 +115,86 @@ def dense_crf(images, masks, zero_unsure=True, return_q=False):
         out = out.cpu().numpy()
         Qout = Qout.cpu().numpy() if return_q else None
     return (out, Qout) if return_q else out
+
+
+def unary_from_softmax(sm, scale=None, clip=1e-5):
+    """pydensecrf.utils.unary_from_softmax [pydensecrf-semantics]: probabilities [C, ...] -> float32 [C, N] energies
+    -log(p).  With `scale` the probabilities are mixed with the uniform distribution first, p = scale * p +
+    (1 - scale) / C (how much the scores are trusted); with `clip` they are then clipped to [clip, 1], which bounds the
+    energy of a class the network rules out.  The host twin of dl3_crf_unary_*."""
+    sm = np.asarray(sm)
+    C = sm.shape[0]
+    if scale is not None:
+        sm = scale * sm + (1.0 - scale) / C
+    if clip is not None:
+        sm = np.clip(sm, clip, 1.0)
+    with np.errstate(divide="ignore"):
+        return (-np.log(sm)).reshape(C, -1).astype(np.float32)
+
+
+def _none_as_zero(v):
+    """scale / clip of the C ABI: a value <= 0 stands for None"""
+    return 0.0 if v is None else float(v)
+
+
+def images_u8(images, dev):
+    """the CRF's image operand: uint8 [B,H,W,3] on `dev`, cast as dense_crf casts it"""
+    import torch
+    if torch.is_tensor(images):
+        return images.to(dev).to(torch.uint8).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype("uint8"))).to(dev)
+
+
+def unary_plain(x, is_prob, scale=None, clip=1e-5):
+    """dl3_crf_unary_plain on the current stream: x float32 cuda [B,N,C] (logits, or probabilities with is_prob) ->
+    U float32 cuda [B,C,N]"""
+    import torch
+    B, N, C = x.shape
+    U = torch.empty(B, C, N, dtype=torch.float32, device=x.device)
+    capi.call("dl3_crf_unary_plain", x.data_ptr(), int(bool(is_prob)), U.data_ptr(), B, N, C, _none_as_zero(scale),
+              _none_as_zero(clip), torch.cuda.current_stream().cuda_stream)
+    return U
+
+
+def dense_crf_softmax(images, probs=None, logits=None, scale=None, clip=1e-5, return_q=False):
+    """The dense CRF on the network's class scores, for a batch of images of one size: images [B,H,W,3] (cast to uint8),
+    and exactly one of `probs` (what Model.predict returns) / `logits`, [B,H,W,C] or [B,H*W,C]; numpy arrays or cuda
+    tensors.  One dl3_crf_unary_plain launch (unary_from_softmax with `scale` / `clip`) and one dl3_crf_inference launch
+    sequence with L = C labels and utils.CRF_PARAMS.
+
+    Returns the MAP class ids, int64 [B,H,W] — a cuda tensor when the scores are one, else a numpy array — and with
+    return_q also Q [B,C,H*W].  C > 32 raises capi.DL3Error; with a single class every pixel is class 0."""
+    import torch
+    from .utils import CRF_PARAMS
+    if (probs is None) == (logits is None):
+        raise ValueError("dense_crf_softmax takes exactly one of probs= and logits=")
+    x = logits if probs is None else probs
+    if not torch.cuda.is_available():
+        raise capi.DL3Error("the device dense-CRF needs a GPU (HIP device); there is no CPU fallback")
+    if len(images.shape) != 4 or images.shape[3] != 3:
+        raise ValueError("images must be [B,H,W,3], got shape %r" % (tuple(images.shape),))
+    B, H, W = (int(n) for n in images.shape[:3])
+    on_device = torch.is_tensor(x)
+    if tuple(x.shape[:-1]) not in ((B, H, W), (B, H * W)):
+        raise ValueError("scores must be [B,H,W,C] or [B,H*W,C] matching images %r, got %r"
+                         % (tuple(images.shape), tuple(x.shape)))
+    C = int(x.shape[-1])
+    if C > MAX_LABELS:
+        raise capi.DL3Error("dense_crf_softmax: %d classes; the device kernels take at most %d labels" % (C, MAX_LABELS))
+    dev = x.device if on_device else torch.device("cuda", torch.cuda.current_device())
+    if on_device:
+        xd = x.to(torch.float32).reshape(B, H * W, C).contiguous()
+    else:
+        xd = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32).reshape(B, H * W, C))).to(dev)
+    im = images_u8(images, dev)
+    if C == 1:
+        out = torch.zeros(B, H, W, dtype=torch.int64, device=dev)
+        Q = torch.ones(B, 1, H * W, dtype=torch.float32, device=dev) if return_q else None
+    else:
+        U = unary_plain(xd, probs is not None, scale, clip)
+        MAP, Q, _ = inference(im, U, CRF_PARAMS["iterations"], want_q=return_q)
+        out = MAP.to(torch.int64).reshape(B, H, W)
+    if not on_device:
+        out = out.cpu().numpy()
+        Q = Q.cpu().numpy() if return_q else None
+    return (out, Q) if return_q else out

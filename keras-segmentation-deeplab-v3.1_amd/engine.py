@@ -1291,25 +1291,17 @@ class Engine:
         v = self.logits_view
         M, C, B, lib = v.buf.M, v.C, self.B, self.lib
         ops = list(self.ops_fwd)
-        last = self.units[-1] if self.units else None
-        form = None
-        if last is not None and last.outv.buf is v.buf and ops and not last.inv.aff and last.inv.act == ACT_NONE \
-                and last.inv.off == 0:
-            if isinstance(last, ResizeUnit) and ops[-1][0] == "dl3_resize_bilinear_fwd" and last.inv.ld == C:
-                _, Hi, Wi, Ho, Wo, _ = last.dims
-                P = lib.dl3_eval_tail_bilinear_partials(B, Hi, Wi, Ho, Wo, C)
-                if P > 0:
-                    form, src, dims = "bilinear", last.inv.p(), (B, Hi, Wi, Ho, Wo, C)
-            elif isinstance(last, ShuffleUnit) and ops[-1][0] == "dl3_phase_shift" \
-                    and last.inv.ld == last.co * last.r * last.r and last.co == C:
-                P = lib.dl3_eval_tail_shuffle_partials(B, last.inv.buf.H, last.inv.buf.W, C, last.r)
-                if P > 0:
-                    form, src, dims = "shuffle", last.inv.p(), (B, last.inv.buf.H, last.inv.buf.W, C, last.r)
-        if form is None:
+        form, src, dims = self._tail_source()
+        if form != "plain":
+            # the fused kernel's own limits (C <= 32, LDS staging): its *_partials query answers 0 for a shape it refuses
+            P = getattr(lib, "dl3_eval_tail_%s_partials" % form)(*dims)
+            if P <= 0:
+                form = "plain"
+        if form == "plain":
             P = lib.dl3_eval_tail_plain_partials(B, M // B, C)
             if P <= 0:
                 raise capi.DL3Error("dl3_eval_tail_plain does not support %d classes" % C)
-            form, src, dims = "plain", ptr(v.buf.t), (B, M // B, C)
+            src, dims = ptr(v.buf.t), (B, M // B, C)
         else:
             ops.pop()
         # labels / weights of the batch (set_targets), the tail's own buffers and ONE record of its results:
@@ -1323,6 +1315,25 @@ class Engine:
                   results=torch.zeros(8, rec_bytes, dtype=torch.uint8, device=self.device))
         self._eval = ev
         return ev
+
+    def _tail_source(self):
+        """what a fused tail (evaluation, CRF unary) may read instead of the full-resolution logits: ("bilinear", pointer,
+        (B, Hi, Wi, Ho, Wo, C)) when the forward plan ends in dl3_resize_bilinear_fwd over materialised low-resolution
+        logits, ("shuffle", pointer, (B, H, W, C, r)) when it ends in dl3_phase_shift over the Subpixel convolution's
+        output — the tail then runs the plan without that last launch —, else ("plain", the head's logits, (B, HW, C))"""
+        v = self.logits_view
+        C, B = v.C, self.B
+        ops = self.ops_fwd
+        last = self.units[-1] if self.units else None
+        if last is not None and last.outv.buf is v.buf and ops and not last.inv.aff and last.inv.act == ACT_NONE \
+                and last.inv.off == 0:
+            if isinstance(last, ResizeUnit) and ops[-1][0] == "dl3_resize_bilinear_fwd" and last.inv.ld == C:
+                _, Hi, Wi, Ho, Wo, _ = last.dims
+                return "bilinear", last.inv.p(), (B, Hi, Wi, Ho, Wo, C)
+            if isinstance(last, ShuffleUnit) and ops[-1][0] == "dl3_phase_shift" \
+                    and last.inv.ld == last.co * last.r * last.r and last.co == C:
+                return "shuffle", last.inv.p(), (B, last.inv.buf.H, last.inv.buf.W, C, last.r)
+        return "plain", ptr(v.buf.t), (B, v.buf.M // B, C)
 
     def eval_op_names(self, confusion=None, mask=False):
         """the launch names of the evaluation plan (tests: no final resize / phase shift / softmax in it)"""
@@ -1403,6 +1414,68 @@ class Engine:
         nnz = np.ascontiguousarray(raw[:, 8 * B:12 * B]).view(np.int32).reshape(n, B)
         counts = np.ascontiguousarray(raw[:, 12 * B:12 * B + 12 * B * C]).view(np.int32).reshape(n, B, 3, C)
         return loss, nnz, counts
+
+    # ------------------------------------------------------------------ CRF unary plan (softmax unary)
+    def _crf_setup(self):
+        """the plan behind crf_unary: like the evaluation plan, the forward op list minus the final resize / phase-shift
+        launch where that launch only spreads materialised low-resolution logits (`ops_fwd` itself stays as it is), ending
+        in dl3_crf_unary_bilinear / _shuffle on those; any other graph keeps its whole forward plan and ends in
+        dl3_crf_unary_plain on the head's logits.  No softmax launch either way."""
+        cp = getattr(self, "_crf", None)
+        if cp is not None:
+            return cp
+        if self.training:
+            raise RuntimeError("Engine.crf_unary needs an inference engine (training=False)")
+        ops = list(self.ops_fwd)
+        form, src, dims = self._tail_source()
+        if form != "plain":
+            ops.pop()
+        self._crf = dict(form=form, src=src, dims=dims, ops=ops)
+        return self._crf
+
+    def _crf_ops(self, U_ptr, scale, clip):
+        cp = self._crf_setup()
+        sc, cl = (0.0 if scale is None else float(scale)), (0.0 if clip is None else float(clip))
+        name = "dl3_crf_unary_" + cp["form"]
+        if cp["form"] == "plain":
+            args = [cp["src"], 0, U_ptr] + list(cp["dims"]) + [sc, cl]
+        else:
+            args = [cp["src"], U_ptr] + list(cp["dims"]) + [sc, cl]
+        return cp["ops"] + [(name, getattr(self.lib, name), args, None)]
+
+    def crf_unary_op_names(self):
+        """the launch names of the CRF unary plan (tests: which form, and no final resize / phase shift / softmax)"""
+        return [rec[0] for rec in self._crf_ops(None, None, 1e-5)]
+
+    def crf_unary(self, U=None, scale=None, clip=1e-5):
+        """forward pass on the resident input (set_input) straight into the dense CRF's unary energies: U [B,C,N] float32
+        on the device (allocated when not given), unary_from_softmax(softmax(logits), scale, clip) of the full-resolution
+        logits — which, like the probabilities, are not written where the head ends in a resize or a phase shift."""
+        C, N = self.logits_view.C, self.logits_view.buf.M // self.B
+        if U is None:
+            U = torch.empty(self.B, C, N, dtype=torch.float32, device=self.device)
+        elif (not torch.is_tensor(U) or U.dtype != torch.float32 or tuple(U.shape) != (self.B, C, N)
+              or not U.is_contiguous() or U.device != self.device):
+            raise ValueError("U must be a contiguous float32 [%d,%d,%d] tensor on %s" % (self.B, C, N, self.device))
+        self._prep()
+        self.run_ops(self._crf_ops(U.data_ptr(), scale, clip))
+        return U
+
+    def crf_mask(self, images, scale=None, clip=1e-5):
+        """crf_unary + dl3_crf_inference (utils.CRF_PARAMS) with `images` [B,H,W,3] as the CRF's image: the MAP class ids,
+        int32 [B,H,W] on the device.  A single-class model has nothing to infer."""
+        from . import crf
+        from .utils import CRF_PARAMS
+        v = self.logits_view
+        if v.C > crf.MAX_LABELS:
+            raise capi.DL3Error("crf_mask: %d classes; the device kernels take at most %d labels" % (v.C, crf.MAX_LABELS))
+        if v.C == 1:
+            return torch.zeros(self.B, v.buf.H, v.buf.W, dtype=torch.int32, device=self.device)
+        im = crf.images_u8(images, self.device)
+        if tuple(im.shape) != (self.B, v.buf.H, v.buf.W, 3):
+            raise ValueError("images must be [%d,%d,%d,3], got %r" % (self.B, v.buf.H, v.buf.W, tuple(im.shape)))
+        MAP, _, _ = crf.inference(im, self.crf_unary(None, scale, clip), CRF_PARAMS["iterations"])
+        return MAP.reshape(self.B, v.buf.H, v.buf.W)
 
     def fwd_bwd(self):
         """forward + loss + backward on the resident batch (the benchmarked hot path)"""

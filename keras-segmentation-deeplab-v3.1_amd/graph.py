@@ -574,13 +574,20 @@ class Model:
             outs.append(eng.predict(xb))
         return np.concatenate(outs, axis=0)
 
-    def predict_mask(self, x, batch_size=32, crf=False):
+    def predict_mask(self, x, batch_size=32, crf=False, crf_unary="labels"):
         """np.argmax(model.predict(x), -1) (notebook cell 9) without shipping the probabilities to the host: the argmax
         runs on the device (dl3_argmax) and only the int32 masks [B,H,W] cross PCIe — 1 MB instead of 22 MB per
         512x512x21 image.  Not part of the reference's Model API.
 
         crf=True: the notebook's `do_crf(image, mask)` step on the device as well — every batch's masks go through
-        crf.dense_crf with `x` as the image (zero_unsure=True, the reference's default) before they are copied out."""
+        crf.dense_crf with `x` as the image (zero_unsure=True, the reference's default) before they are copied out.
+
+        crf_unary (only looked at with crf=True): "labels" is that path — the unary term rebuilt from the arg-max mask
+        with gt_prob; "softmax" hands the CRF the network's own class probabilities (unary_from_softmax, one label per
+        class): forward pass, Engine.crf_unary and dl3_crf_inference follow each other on the device and only the int32
+        masks are copied out."""
+        if crf and crf_unary not in ("labels", "softmax"):
+            raise ValueError("predict_mask: crf_unary must be 'labels' or 'softmax', got %r" % (crf_unary,))
         if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
             x = np.asarray(x, np.float32)
         n = x.shape[0]
@@ -590,6 +597,9 @@ class Model:
             xb = x[i:i + bs]
             eng = self._engine(xb.shape[0], False)
             eng.set_input(xb)
+            if crf and crf_unary == "softmax":
+                outs.append(eng.crf_mask(xb).to("cpu").numpy())
+                continue
             eng.forward()
             if crf:
                 from .crf import dense_crf

@@ -173,6 +173,15 @@ def do_crf(im, mask, zero_unsure=True, backend="pydensecrf"):
     return restore_crf_labels(MAP, colors)
 
 
+def do_crf_softmax(im, probs, scale=None, clip=1e-5):
+    """do_crf with the network's class probabilities as the unary term instead of a label mask (DeepLab's own CRF step;
+    pydensecrf.utils.unary_from_softmax): im [H,W,3], probs [H,W,C] or [H*W,C] -> class ids int64 [H,W].  Runs on the
+    GPU (crf.dense_crf_softmax) with the kernel parameters and iteration count of CRF_PARAMS."""
+    from .crf import dense_crf_softmax
+    probs = np.asarray(probs)
+    return dense_crf_softmax(np.asarray(im)[None], probs=probs.reshape((1,) + probs.shape), scale=scale, clip=clip)[0]
+
+
 class SegmentationGenerator:
     """The tensor contract of the reference's `SegmentationGenerator` (utils.py:257-409) over IN-MEMORY arrays:
     `gen[i]` -> `(X [B,H,W,3] float32, Y [B,HW,1], {'pred_mask': SW [B,HW]})`, `len(gen)` batches, `on_epoch_end()`

@@ -379,6 +379,34 @@ int dl3_adam_step(float *p, const float *g, float *m, float *v, size_t n, float 
 int dl3_adam_step_norm(float *p, const float *g, float *m, float *v, size_t n, float lr_t, float beta1, float beta2,
                        float eps, float grad_scale, const float *denom, void *stream);
 
+/* ---- the optimizer step beyond plain Adam --------------------------------------------------------------
+ * [TF-semantics: Keras 2.2.4 keras/optimizers.py, restated from memory.]
+ * dl3_grad_sumsq: out[0] (double, device) = sum of g[i]^2 over [0, n).  Two launches: per-workgroup partial sums
+ * accumulated in double into `workspace` (dl3_grad_sumsq_workspace_bytes(n), 8-byte aligned), then ONE workgroup folds
+ * them in a fixed order — no float atomics, bit-reproducible from run to run.  16-byte loads where g is 16-byte aligned.
+ * -3 (DL3_EWORKSPACE) on a short workspace. */
+size_t dl3_grad_sumsq_workspace_bytes(size_t n);
+int dl3_grad_sumsq(const float *g, size_t n, double *out, void *workspace, size_t workspace_bytes, void *stream);
+/* dl3_opt_step: ONE launch over [0, n).  The effective gradient (Optimizer.get_gradients), built on the device:
+ *   sc = grad_scale / max(denom[0], 1e-20) when denom is given (dl3_adam_step_norm's semantics), else grad_scale
+ *   clipnorm > 0: norm = sc * sqrt(sumsq[0]) (sumsq: the result of dl3_grad_sumsq over the SAME g — the GLOBAL norm);
+ *                 g' = g * sc * (clipnorm / norm) when norm >= clipnorm, else g * sc
+ *   clipvalue > 0: g' clamped to [-clipvalue, clipvalue]
+ * and the rule (lr_t from the host: lr / (1 + decay * iterations), for Adam times the bias correction):
+ *   DL3_OPT_SGD     c0 = momentum: v = c0*s0 - lr_t*g'; s0 <- v; p += v, or with nesterov p += c0*v - lr_t*g'
+ *   DL3_OPT_RMSPROP c0 = rho:      s0 <- c0*s0 + (1-c0)*g'^2; p -= lr_t*g' / (sqrt(s0) + eps)
+ *   DL3_OPT_ADAM    c0, c1 = beta_1, beta_2; s0 = m, s1 = v: dl3_adam_step's arithmetic on g'
+ * s1 may be NULL for the one-slot rules.  fp32 throughout; nothing is read back to the host. */
+#define DL3_OPT_SGD 0
+#define DL3_OPT_RMSPROP 1
+#define DL3_OPT_ADAM 2
+typedef struct {
+  float lr_t, c0, c1, eps, grad_scale, clipnorm, clipvalue; /* clipnorm / clipvalue: 0 = off */
+  int nesterov;
+} dl3_opt_hyper;
+int dl3_opt_step(float *p, const float *g, float *s0, float *s1, size_t n, int rule, const dl3_opt_hyper *hyper,
+                 const float *denom, const double *sumsq, void *stream);
+
 /* ---- either side of the network: targets in, metric counts out -------------------------- */
 #define DL3_LABEL_U8 0  /* cv2.imread(path, 0) label maps (utils.py:314) */
 #define DL3_LABEL_I32 1 /* label.astype('int32') (utils.py:371) */

@@ -1,6 +1,6 @@
 """The callbacks the reference's training call uses (segmentation.ipynb cell 5; `from utils import *` provides them
 through `from keras.callbacks import *`): Callback, History, LambdaCallback, ModelCheckpoint, EarlyStopping,
-ReduceLROnPlateau — Keras 2.2.4 constructor signatures, defaults and decision rules [TF-semantics, restated from
+ReduceLROnPlateau, LearningRateScheduler — Keras 2.2.4 constructor signatures, defaults and decision rules [TF-semantics, restated from
 memory of keras/callbacks.py 2.2.4; the package is not installed].  Pure host-side control plane: nothing here touches
 the device except through the model's own methods (save_weights, get_weights / set_weights, the learning rate).
 
@@ -11,6 +11,8 @@ What differs from Keras, on purpose:
   * The learning rate is read / written through `model._get_lr()` / `model._set_lr(v)`: the compiled hyper-parameter
     dict and the optimizer object's `lr`; the change takes effect at the next step, without a new engine.
   * TensorBoard is not built.
+  * poly_decay(base_lr, max_epochs, power) is not in Keras: the "poly" schedule DeepLab is trained with, as a function
+    LearningRateScheduler takes.
 """
 import warnings
 
@@ -299,3 +301,41 @@ class ReduceLROnPlateau(Callback):
                         print("\nEpoch %05d: ReduceLROnPlateau reducing learning rate to %s." % (epoch + 1, new_lr))
                     self.cooldown_counter = self.cooldown
                     self.wait = 0
+
+
+class LearningRateScheduler(Callback):
+    """keras.callbacks.LearningRateScheduler (2.2.4): at the start of every epoch the learning rate becomes
+    schedule(epoch, lr) — or schedule(epoch), the older one-argument form, when the call with two raises TypeError; the
+    result must be a float.  Adds logs['lr'] at the end of the epoch."""
+
+    def __init__(self, schedule, verbose=0):
+        super().__init__()
+        self.schedule, self.verbose = schedule, verbose
+
+    def on_epoch_begin(self, epoch, logs=None):
+        lr = float(self.model._get_lr())
+        try:  # new API
+            lr = self.schedule(epoch, lr)
+        except TypeError:  # old API for backward compatibility
+            lr = self.schedule(epoch)
+        if not isinstance(lr, (float, np.float32, np.float64)):
+            raise ValueError('The output of the "schedule" function should be float.')
+        self.model._set_lr(float(lr))
+        if self.verbose > 0:
+            print("\nEpoch %05d: LearningRateScheduler setting learning rate to %s." % (epoch + 1, lr))
+
+    def on_epoch_end(self, epoch, logs=None):
+        if logs is not None:
+            logs["lr"] = float(self.model._get_lr())
+
+
+def poly_decay(base_lr, max_epochs, power=0.9):
+    """the "poly" learning-rate policy of the DeepLab papers, per epoch: schedule(epoch) = base_lr * (1 - epoch /
+    max_epochs) ** power (0 from max_epochs on) — for LearningRateScheduler"""
+    base_lr, max_epochs, power = float(base_lr), int(max_epochs), float(power)
+    if not (max_epochs > 0 and base_lr >= 0 and power > 0):
+        raise ValueError("poly_decay: max_epochs, power must be > 0 and base_lr >= 0")
+
+    def schedule(epoch, lr=None):
+        return base_lr * max(1.0 - float(epoch) / max_epochs, 0.0) ** power
+    return schedule

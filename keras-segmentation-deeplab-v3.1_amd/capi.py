@@ -30,6 +30,8 @@ _CTYPES = {
     "const long long *": ctypes.c_void_p,
     "long long *": ctypes.c_void_p,
     "double *": ctypes.c_void_p,
+    "const double *": ctypes.c_void_p,
+    "const dl3_opt_hyper *": ctypes.c_void_p,   # host pointer: ctypes.byref(OptHyper)
     "unsigned long long *": ctypes.c_void_p,
     "const unsigned long long *": ctypes.c_void_p,
     "const char *": ctypes.c_char_p,
@@ -40,6 +42,15 @@ _CTYPES = {
     "unsigned long long": ctypes.c_ulonglong,
     "void": None,
 }
+
+
+OPT_SGD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2
+
+
+class OptHyper(ctypes.Structure):
+    """dl3_opt_hyper of include/dl3.h (the layout is checked against the header by tests/test_optimizers_host.py)"""
+    _fields_ = [(k, ctypes.c_float) for k in ("lr_t", "c0", "c1", "eps", "grad_scale", "clipnorm", "clipvalue")] + [
+        ("nesterov", ctypes.c_int)]
 
 
 def _norm_type(t):

@@ -13,6 +13,7 @@ Design (MI355X-first):
     BN-backward partial sums), residual Adds are gradient aliases.
 Reference call stack being replaced: Keras Model.predict / train_on_batch -> TF Session.run.
 """
+import ctypes
 import math
 import os
 
@@ -330,8 +331,13 @@ class Engine:
         self.tail = (max(np_, 4) + 3) // 4 * 4
         if self.training:
             self.grads = self.zeros(self.tail + 4)
+            # optimizer slots 0 / 1: Adam's m / v; SGD's momentum buffer and RMSprop's accumulator live in slot 0
             self.adam_m = self.zeros(max(np_, 4))
             self.adam_v = self.zeros(max(np_, 4))
+            # the global gradient norm of clipnorm (dl3_grad_sumsq): per-workgroup partials and the 8-byte result
+            ws = int(self.lib.dl3_grad_sumsq_workspace_bytes(max(np_, 4)))
+            self.sumsq_ws = torch.zeros((ws + 7) // 8, dtype=torch.float64, device=self.device)
+            self.grad_sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
             self.dummy_grad = self.zeros(4096)
         self.sync_all_to_device()
 
@@ -1507,34 +1513,74 @@ class Engine:
         else:
             self.run_ops(self.ops_bwd)
 
-    def adam(self, opt=None, grad_scale=1.0, norm=None):
-        """Keras Adam with decay (notebook cell 2): lr_t = lr/(1+decay*it) * sqrt(1-b2^t)/(1-b1^t).
+    _RULES = {
+        "adam": (capi.OPT_ADAM, dict(lr=7e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=1e-6)),   # the notebook's values
+        "sgd": (capi.OPT_SGD, dict(lr=0.01, momentum=0.0, decay=0.0, nesterov=False)),
+        "rmsprop": (capi.OPT_RMSPROP, dict(lr=0.001, rho=0.9, epsilon=1e-7, decay=0.0)),
+    }
+
+    def opt_step(self, opt=None, grad_scale=1.0, norm=None):
+        """one optimizer step over the parameter arena.  opt: the compiled description dict(rule='adam' | 'sgd' |
+        'rmsprop', hyper={...}, clipnorm=, clipvalue=) (graph.Model._opt_desc), or — Engine.adam's argument — the plain
+        Adam hyper-parameter dict / None.  [TF-semantics: Keras 2.2.4 get_updates, from memory] lr = lr / (1 + decay * it)
+        with `it` the iteration count BEFORE the increment; Adam folds the bias correction sqrt(1-b2^t)/(1-b1^t), t = it + 1,
+        into lr_t.  An unclipped Adam is dl3_adam_step / dl3_adam_step_norm; every other case is dl3_opt_step, with
+        dl3_grad_sumsq in front of it when clipnorm is set (the global norm stays on the device).
         norm (the default on data-parallel / external_nnz engines, and the only valid choice there): the gradient scale is
-        finished on the device, normaliser / count_all from the arena tail (dl3_adam_step_norm); grad_scale is ignored.
-        An external_nnz engine's loss kernel divides by the FIXED c0, so adam(opt, scale) without norm would silently
-        apply grad * scale / c0 instead of grad / count_all: refused."""
+        finished on the device, normaliser / count_all from the arena tail; grad_scale is ignored.
+        An external_nnz engine's loss kernel divides by the FIXED c0, so a step with a host scale and without norm would
+        silently apply grad * scale / c0 instead of grad / count_all: refused."""
         if norm is None:
             norm = self.external_nnz
         if self.external_nnz and not norm:
             raise ValueError("Engine.adam(norm=False) on an external_nnz (data-parallel) engine: its gradients are "
                              "normalised by a fixed constant and must be finished by dl3_adam_step_norm")
-        o = dict(lr=7e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=1e-6)
-        o.update(opt or {})
+        if not (opt and "rule" in opt):
+            opt = dict(rule="adam", hyper=opt)
+        rule = opt["rule"]
+        if rule not in self._RULES:
+            raise ValueError("Engine.opt_step: unknown rule %r (known: %s)" % (rule, sorted(self._RULES)))
+        rid, defaults = self._RULES[rule]
+        o = dict(defaults)
+        o.update(opt.get("hyper") or {})
+        clipnorm, clipvalue = float(opt.get("clipnorm") or 0.0), float(opt.get("clipvalue") or 0.0)
         it = self.iteration
         t = it + 1
-        lr = o["lr"] / (1.0 + o["decay"] * it)
-        lr_t = lr * math.sqrt(1.0 - o["beta_2"] ** t) / (1.0 - o["beta_1"] ** t)
+        lr_t = o["lr"] / (1.0 + o["decay"] * it)
+        if rule == "adam":
+            lr_t = lr_t * math.sqrt(1.0 - o["beta_2"] ** t) / (1.0 - o["beta_1"] ** t)
         if norm:
             assert self.external_nnz
-            capi.call("dl3_adam_step_norm", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
-                      self.n_param, lr_t, o["beta_1"], o["beta_2"], o["epsilon"], self.nnz_host,
-                      self.grads.data_ptr() + 4 * self.tail, torch.cuda.current_stream().cuda_stream)
+            grad_scale, denom = self.nnz_host, self.grads.data_ptr() + 4 * self.tail
         else:
-            capi.call("dl3_adam_step", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
-                      self.n_param, lr_t, o["beta_1"], o["beta_2"], o["epsilon"], grad_scale,
-                      torch.cuda.current_stream().cuda_stream)
+            denom = None
+        stream = torch.cuda.current_stream().cuda_stream
+        if rule == "adam" and not clipnorm and not clipvalue:
+            if norm:
+                capi.call("dl3_adam_step_norm", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
+                          self.n_param, lr_t, o["beta_1"], o["beta_2"], o["epsilon"], grad_scale, denom, stream)
+            else:
+                capi.call("dl3_adam_step", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
+                          self.n_param, lr_t, o["beta_1"], o["beta_2"], o["epsilon"], grad_scale, stream)
+        else:
+            if clipnorm:
+                # the norm of what the optimizer updates: [0, n_param) — the arena's padding holds exact zeros
+                capi.call("dl3_grad_sumsq", ptr(self.grads), self.n_param, self.grad_sumsq.data_ptr(),
+                          self.sumsq_ws.data_ptr(), self.sumsq_ws.numel() * 8, stream)
+            c0, c1 = {"adam": (o.get("beta_1"), o.get("beta_2")), "sgd": (o.get("momentum"), 0.0),
+                      "rmsprop": (o.get("rho"), 0.0)}[rule]
+            h = capi.OptHyper(lr_t, c0, c1, o.get("epsilon", 0.0), grad_scale, clipnorm, clipvalue,
+                              int(bool(o.get("nesterov", False))))
+            capi.call("dl3_opt_step", ptr(self.params), ptr(self.grads), ptr(self.adam_m),
+                      ptr(self.adam_v) if rule == "adam" else None, self.n_param, rid, ctypes.byref(h), denom,
+                      self.grad_sumsq.data_ptr() if clipnorm else None, stream)
         self.iteration += 1
         self.dirty = True
+
+    def adam(self, opt=None, grad_scale=1.0, norm=None):
+        """Keras Adam with decay (notebook cell 2): lr_t = lr/(1+decay*it) * sqrt(1-b2^t)/(1-b1^t); opt_step with the
+        plain hyper-parameter dict (None: the notebook's values)"""
+        self.opt_step(opt, grad_scale, norm)
 
     def adopt_optimizer_state(self, other):
         """continue another training engine's optimizer (same model, other batch size): Adam moments, iteration count
@@ -1565,12 +1611,12 @@ class Engine:
         if self.external_nnz:
             if comm is not None:
                 comm.allreduce_grads(self.grads)
-            self.adam(opt, norm=True)
+            self.opt_step(opt, norm=True)
         else:
             scale = 1.0
             if comm is not None:
                 scale = comm.allreduce_grads(self.grads)
-            self.adam(opt, scale)
+            self.opt_step(opt, scale)
         return self.loss_handle() if lazy else self.loss_value()
 
     def grad_of(self, name):

@@ -460,11 +460,14 @@ class Model:
         """keras Model.compile as used by the notebook (cell 2): remembers the optimizer
         hyper-parameters; the loss on the path is always sparse_crossentropy_ignoring_last_label
         with temporal sample weights (utils.py:127-130)."""
-        from .optimizers import as_adam_dict
-        # optimizer: None (the notebook's Adam(lr=7e-4, epsilon=1e-8, decay=1e-6)), a dict of overrides, 'adam', or an
-        # optimizers.Adam / any Keras-style Adam exposing get_config(); anything else raises here, not at the first step
-        self._compiled = dict(optimizer=as_adam_dict(optimizer), optimizer_object=optimizer, loss=loss, metrics=metrics,
-                              sample_weight_mode=sample_weight_mode)
+        from .optimizers import compile_optimizer
+        # optimizer: None (the notebook's Adam(lr=7e-4, epsilon=1e-8, decay=1e-6)), a dict of overrides, 'adam', an
+        # optimizers.Adam / any Keras-style Adam exposing get_config(), or an optimizers.SGD / RMSprop (instances of this
+        # package's classes only); anything else raises here, not at the first step.  The rule and the clip settings sit
+        # beside the hyper-parameter dict, which for Adam stays the five-key dict it always was
+        rule, hyper, clipnorm, clipvalue = compile_optimizer(optimizer)
+        self._compiled = dict(optimizer=hyper, optimizer_object=optimizer, loss=loss, metrics=metrics,
+                              sample_weight_mode=sample_weight_mode, rule=rule, clipnorm=clipnorm, clipvalue=clipvalue)
         # Keras 2.2.4 collects the weights the optimizer updates HERE (`_collected_trainable_weights`), and the layers'
         # update ops (BatchNormalization moving statistics) when the train function is first built — the first
         # train_on_batch / fit after compile().  `layer.trainable` flipped in between (segmentation.ipynb: compile in
@@ -750,13 +753,24 @@ class Model:
             return logs
         return validate
 
+    def _opt_desc(self):
+        """the compiled optimizer as Engine.opt_step takes it; `hyper` IS the compiled dict, so _set_lr shows at the next
+        step.  Nothing compiled: the notebook's Adam."""
+        c = self._compiled
+        if c is None:
+            return dict(rule="adam", hyper={})
+        return dict(rule=c.get("rule", "adam"), hyper=c["optimizer"], clipnorm=c.get("clipnorm"), clipvalue=c.get("clipvalue"))
+
     def _get_lr(self):
-        opt = (self._compiled or {}).get("optimizer") or {}
-        return float(opt.get("lr", 7e-4))   # Engine.adam's default: the notebook's Adam(lr=7e-4)
+        from .engine import Engine
+        c = self._compiled or {}
+        # (a rule's default where the compiled dict names no lr; Adam's: the notebook's Adam(lr=7e-4))
+        return float((c.get("optimizer") or {}).get("lr", Engine._RULES[c.get("rule", "adam")][1]["lr"]))
 
     def _set_lr(self, lr):
-        """a new learning rate from the next step on: the compiled hyper-parameter dict (Engine.adam takes it per call —
-        no new engine, Adam's moments and iteration untouched) and the optimizer object's `lr` if there is one"""
+        """a new learning rate from the next step on, whatever the rule: the compiled hyper-parameter dict
+        (Engine.opt_step takes it per call — no new engine, the slots and the iteration untouched) and the optimizer
+        object's `lr` if there is one"""
         if self._compiled is None:
             self._compiled = dict(optimizer={}, optimizer_object=None, loss=None, metrics=None, sample_weight_mode=None)
         self._compiled["optimizer"]["lr"] = float(lr)
@@ -810,7 +824,7 @@ class Model:
                     sample_weight = sample_weight[lo:hi]
             engine_kw = dict(engine_kw, external_nnz=True)
         eng = self._engine(x.shape[0], True, **engine_kw)
-        opt = (self._compiled or {}).get("optimizer") or {}
+        opt = self._opt_desc()
         if not multi:
             return eng.train_step(x, y, sample_weight, opt, lazy=lazy_loss)
         self._dp_sync_weights(eng)
@@ -896,10 +910,11 @@ class Model:
         raw = hasattr(generator, "raw_batch")
         plan = getattr(generator, "plan", None) if raw else None
         for ep in range(epochs):
-            # read every epoch: a callback (ReduceLROnPlateau) may have changed the learning rate
-            opt = (self._compiled or {}).get("optimizer") or {}
             if ses:
                 ses.epoch_begin(ep)
+            # read every epoch, behind on_epoch_begin: a callback (ReduceLROnPlateau, LearningRateScheduler) may have
+            # changed the learning rate
+            opt = self._opt_desc()
 
             def batches():
                 for i in range(steps):
@@ -944,7 +959,7 @@ class Model:
                     # ONE all-reduce of the arena (gradients + the shard's count(w != 0) and loss sum) behind the replayed
                     # graph, the scale finished on the device (Engine.train_step does the same for host-array batches)
                     dp.allreduce_grads(eng.grads)
-                eng.adam(opt)   # (norm defaults to the engine's external_nnz)
+                eng.opt_step(opt)   # (norm defaults to the engine's external_nnz)
                 losses.append(eng.loss_handle())
                 if ses:
                     ses.batch_end(len(losses) - 1, eng.B, losses[-1])

@@ -18,8 +18,10 @@ from .deeplabv3p import Deeplabv3
 from .graph import Activation, Conv2D, Model, Reshape, ResizeBilinear
 from .subpixel import Subpixel, icnr_weights
 # the reference's `from utils import *` hands the notebook Keras' callbacks (utils.py: `from keras.callbacks import *`)
-from .callbacks import (Callback, EarlyStopping, History, LambdaCallback, ModelCheckpoint,  # noqa: F401
-                        ReduceLROnPlateau)
+from .callbacks import (Callback, EarlyStopping, History, LambdaCallback, LearningRateScheduler,  # noqa: F401
+                        ModelCheckpoint, ReduceLROnPlateau, poly_decay)
+# ... and Keras' optimizers (utils.py:16/31: `from keras.optimizers import Adam, SGD, RMSprop`)
+from .optimizers import SGD, Adam, RMSprop  # noqa: F401
 
 
 def sparse_crossentropy_ignoring_last_label(y_true, y_pred):

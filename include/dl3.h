@@ -520,6 +520,27 @@ int dl3_crf_unary_bilinear(const float *logits_lo, float *U, int B, int Hi, int 
 int dl3_crf_unary_shuffle(const float *u, float *U, int B, int H, int W, int C, int r, float scale, float clip,
                           void *stream);
 
+/* ---- multi-scale and flip inference (Model.predict_multiscale) [deeplab-semantics] ---------------------
+ * Both launches are the align_corners = True bilinear resize, every operation a separately rounded fp32 operation in this
+ * order (no fused multiply-add), per axis with input extent `in` and output extent `out`:
+ *   scale = fl((in - 1) / (out - 1)), 0 where out == 1;  f = fl(o * scale);  lo = min(int(f), in - 1);
+ *   hi = min(lo + 1, in - 1);  w = fl(f - lo);
+ *   top = tl + (tr - tl) * wx;  bot = bl + (br - bl) * wx;  value = top + (bot - top) * wy.
+ * dl3_tta_resize_image: raw pixels src[B][Hi][Wi][3], float32 (DL3_TTA_F32) or uint8 (DL3_TTA_U8), -> float32
+ *   dst[B][Ho][Wo][3], not rounded.  flip = 1: column ox receives the value computed for column Wo - 1 - ox.
+ * dl3_tta_accumulate: one pass's probabilities probs[B][Hi][Wi][C] resized to [B][Ho][Wo][C] and folded into the fp32
+ *   accumulator acc[B][Ho][Wo][C] (any 4-byte alignment; 16-byte accesses between its 16-byte boundaries).  flip = 1: the
+ *   pass ran on a mirrored image, source column x is read at index Wi - 1 - x.  first = 1: acc = v, and acc is NOT read;
+ *   otherwise acc = acc + v.  n_passes_if_last = n > 0: the stored value is (acc + v) / n (v / n when first), a correctly
+ *   rounded fp32 division; 0: not the last pass.  Any C >= 1, any extents >= 1, up- and down-scaling.  No atomics: two runs
+ *   are bit-identical. */
+#define DL3_TTA_F32 0
+#define DL3_TTA_U8 1
+int dl3_tta_resize_image(const void *src, int src_dtype, float *dst, int B, int Hi, int Wi, int Ho, int Wo, int flip,
+                         void *stream);
+int dl3_tta_accumulate(const float *probs, float *acc, int B, int Hi, int Wi, int Ho, int Wo, int C, int flip, int first,
+                       int n_passes_if_last, void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

@@ -225,6 +225,9 @@ def Deeplabv3(weights="pascal_voc", input_tensor=None, infer=False, input_shape=
     x = Activation("softmax")(x)
 
     model = Model(img_input, x, name="deeplabv3p")
+    # the same graph for another input size (Model.predict_multiscale's sibling models)
+    model._tta_rebuild = lambda shape: Deeplabv3(weights=None, input_tensor=None, infer=infer, input_shape=tuple(shape),
+                                                 classes=classes, backbone=backbone, OS=OS, alpha=alpha)
     if weights == "pascal_voc":
         model.load_weights(weights_path(backbone), by_name=True)
     return model

@@ -344,6 +344,9 @@ class Model:
         self._dp = None          # parallel.DataParallel once distribute() was called
         self._dp_synced = False
         self._train_eng = None   # the engine that holds the live Adam moments / iteration / dropout step
+        # callable(input_shape) -> the same graph for another input size, fresh weights: recorded by Deeplabv3() and
+        # SegModel.create_seg_model for predict_multiscale's sibling models (tta.py)
+        self._tta_rebuild = None
 
     # -- graph -----------------------------------------------------------------------
     def _collect(self):
@@ -610,6 +613,29 @@ class Model:
             else:
                 outs.append(eng.argmax())
         return np.concatenate(outs, axis=0)
+
+    def predict_multiscale(self, x, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True, batch_size=8, output="probs",
+                           crf=False, factory=None):
+        """DeepLab's evaluation protocol [deeplab-semantics]: the class probabilities averaged over input
+        scales and left-right flips, every step on the device (tta.py).  A pass at scale s runs this graph built for the
+        input size tta.scaled_size(H, s) x tta.scaled_size(W, s) — a sibling model, built once and kept (clear_multiscale
+        drops them) — on this model's CURRENT weights and moving statistics; the passes run in the order of `scales`, the
+        mirrored one behind the plain one.  Not part of the reference's Model API.
+
+        output="probs": numpy float32 in the shape predict() returns; output="mask": int32 [B,H,W], the first-maximum
+        argmax of the average (dl3_argmax) — only the masks cross PCIe.  crf=True (with "mask" only): the averaged
+        probabilities, still on the device, go through crf.dense_crf_softmax with `x` as the image.
+        x: raw 0-255 pixels [B,H,W,3], float32 or uint8, host array or device tensor, as predict() takes them.
+        factory: callable(input_shape) -> Model, needed for a Model that neither Deeplabv3() nor
+        SegModel.create_seg_model built; without it such a model raises ValueError before any device work."""
+        from . import tta
+        return tta.predict_multiscale(self, x, scales=scales, flip=flip, batch_size=batch_size, output=output, crf=crf,
+                                      factory=factory)
+
+    def clear_multiscale(self):
+        """drop predict_multiscale's sibling models and their engines (each owns an activation arena)"""
+        from . import tta
+        tta.clear_multiscale(self)
 
     def evaluate(self, x, y, batch_size=32, sample_weight=None, verbose=0, device=False):
         """keras Model.evaluate for the notebook's metrics (cell 2: metrics=[Jaccard, sparse_accuracy_ignoring_last_label]):

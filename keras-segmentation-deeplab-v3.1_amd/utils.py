@@ -98,6 +98,22 @@ def calculate_iou(model, X, label, nb_classes=21):
     return np.roll(plain, -1, axis=(0, 1)).astype(float)
 
 
+def calculate_iou_multiscale(model, X, label, nb_classes=21, **tta_kwargs):
+    """calculate_iou with the masks of Model.predict_multiscale in place of the single-scale argmax: the
+    same layout, rolled class 0 included.  The masks come from the device (output="mask"); the matrix is a host bincount
+    over label * nb_classes + prediction of the pixels whose label is below nb_classes.  tta_kwargs: scales, flip,
+    batch_size, crf, factory."""
+    if "output" in tta_kwargs:
+        raise ValueError("calculate_iou_multiscale builds its matrix from masks: output= is not an option")
+    label = np.asarray(label)
+    pred = model.predict_multiscale(X, output="mask", **tta_kwargs).reshape(-1).astype(np.int64)
+    lab = label.reshape(-1).astype(np.int64)
+    C = int(model.output.shape[-1])   # Model.confusion_matrix's extent: the model's classes
+    keep = (lab >= 0) & (lab < min(nb_classes, C))
+    plain = np.bincount(lab[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+    return np.roll(plain, -1, axis=(0, 1)).astype(float)
+
+
 def prepare_targets(labels, n_classes=21):
     """Device-side label half of SegmentationGenerator.__getitem__ (utils.py:375-402): raw label maps
     [B,H,W] or [B,HW] (uint8 / int32; numpy array or cuda tensor) -> (Y [B,HW,1], SW [B,HW]) cuda float32 tensors, ready
@@ -326,6 +342,10 @@ class SegModel:
                 warnings.warn("multi_gpu=True in a single process: this package runs one process per GPU — launch the "
                               "script with `python -m torch.distributed.run --nproc-per-node <gpus>` to use them",
                               RuntimeWarning, stacklevel=2)
+        # the same head for another image size (Model.predict_multiscale's sibling models)
+        dataset = self.mainpath
+        model._tta_rebuild = lambda shape: SegModel(dataset, image_size=tuple(shape[:2])).create_seg_model(
+            net, n=n, backbone=backbone, load_weights=False, multi_gpu=False)
         self.model = model
         return model
 

@@ -541,6 +541,39 @@ int dl3_tta_resize_image(const void *src, int src_dtype, float *dst, int B, int 
 int dl3_tta_accumulate(const float *probs, float *acc, int B, int Hi, int Wi, int Ho, int Wo, int C, int flip, int first,
                        int n_passes_if_last, void *stream);
 
+/* ---- sliding-window inference (Model.predict_sliding) -------------------------------------------------
+ * An image [Hi][Wi][3] of ANY size is cut into overlapping windows of the model's size H x W; the class probabilities of
+ * the windows are averaged where they overlap.  One image per launch; the window grid is arithmetic, per axis (extent
+ * `size`, window `win`, stride 1 <= s <= win):
+ *   P = max(size, win);  n = ceil((P - win) / s) + 1;  window k starts at min(k s, P - win)
+ * (the last window is shifted back to end on the image's edge), window index k = ky * nx + kx.  A launch handles the
+ * windows k0 .. k0 + nw - 1.
+ * dl3_slide_gather: window pixel (r, c) of window k = image pixel (y0 + r, x0 + c) as float32 (src float32, DL3_TTA_F32,
+ *   or uint8, DL3_TTA_U8) into dst[nw][H][W][3]; rows >= Hi and columns >= Wi — an image smaller than the window — hold
+ *   pad_value.
+ * dl3_slide_accumulate: probs[nw][H][W][C] folded into the canvas acc[Hi][Wi][C], which the caller zeroed in front of the
+ *   image's first launch (any 4-byte alignment; 16-byte accesses between its 16-byte boundaries).  Per canvas element, over
+ *   the launch's windows that cover its pixel in ascending k:  t = fl(w p);  acc = fl(acc + t), every operation a
+ *   separately rounded fp32 operation (no fused multiply-add).  blend DL3_SLIDE_UNIFORM: w = 1; DL3_SLIDE_PYRAMID:
+ *   w = fl(float(min(r + 1, H - r)) * float(min(c + 1, W - c))) at window pixel (r, c).  Probabilities at pad positions
+ *   are not read.  Cutting one window sequence into launches differently gives the same bits.  A launch reads and writes
+ *   only canvas pixels inside its own windows.  wsum (nullable) [Hi][Wi], zeroed like acc: ws = fl(ws + w) in the same
+ *   order; NULL: dl3_slide_finalize recomputes it from the geometry, to the same bits.
+ * dl3_slide_finalize: prob = fl(acc / ws), a correctly rounded fp32 division, into probs_out[Hi][Wi][C] (nullable; may
+ *   be acc itself), and mask_out[Hi][Wi] (int32, nullable) = the first maximum of these prob values (dl3_argmax's rule).
+ *   Not both NULL.  wsum NULL: ws is the weight sum of ALL the grid's windows over the pixel, in ascending k.
+ * Any C >= 1, any extents >= 1.  No allocation, no synchronisation, no atomics: capturable, two runs are bit-identical.
+ * -1 for: a stride outside [1, window], k0 + nw beyond the grid, nw < 1, an unknown blend or dtype, both outputs NULL, or
+ * extents beyond the kernels' 32-bit pixel indices (Hi Wi, nw H W, Wi C < 2^31; C <= 65536). */
+#define DL3_SLIDE_UNIFORM 0
+#define DL3_SLIDE_PYRAMID 1
+int dl3_slide_gather(const void *src, int src_dtype, int Hi, int Wi, int H, int W, int sh, int sw, int k0, int nw,
+                     float pad_value, float *dst, void *stream);
+int dl3_slide_accumulate(const float *probs, float *acc, float *wsum, int Hi, int Wi, int H, int W, int C, int sh, int sw,
+                         int k0, int nw, int blend, void *stream);
+int dl3_slide_finalize(const float *acc, const float *wsum, float *probs_out, int *mask_out, int Hi, int Wi, int H, int W,
+                       int C, int sh, int sw, int blend, void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

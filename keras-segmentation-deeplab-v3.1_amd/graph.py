@@ -637,6 +637,27 @@ class Model:
         from . import tta
         tta.clear_multiscale(self)
 
+    def predict_sliding(self, x, stride=None, blend="uniform", batch_size=8, output="mask", pad_value=127.5):
+        """Sliding-window inference: masks or probabilities for images of ANY size at their own resolution.
+        Every image is cut into overlapping windows of the model's input size (H, W) — the last window of an axis is
+        shifted back to end on the image's edge, an image smaller than the window is padded with `pad_value` (127.5, the
+        pixel the pre-scale maps to 0) — the network runs on the windows, their class probabilities are averaged where
+        they overlap and the arg-max is taken per image pixel, every step on the device (slide.py).  Not part of the
+        reference's Model API.
+
+        x: raw 0-255 pixels, uint8 or float32, host array or device tensor [B,Hi,Wi,3], or a list / tuple of [Hi,Wi,3]
+        images of different sizes.  stride: an integer or (sh, sw), 1 <= stride <= window; default two thirds of the
+        window.  blend: "uniform" (the plain mean) or "pyramid" (weights min(r+1, H-r) * min(c+1, W-c), which
+        down-weight a window's border).  batch_size: windows per forward pass; the windows of all images form one list
+        (image-major), so chunks span images.  output="mask": int32 [Hi,Wi], the first-maximum arg-max of the averaged
+        probabilities — only the masks cross PCIe; output="probs": float32 [Hi,Wi,C].  Stacked into one array for array
+        input, a list for list input.  Bad arguments raise ValueError before any device work.
+
+        Out of scope: combining with predict_multiscale, crf=, training, reading image files."""
+        from . import slide
+        return slide.predict_sliding(self, x, stride=stride, blend=blend, batch_size=batch_size, output=output,
+                                     pad_value=pad_value)
+
     def evaluate(self, x, y, batch_size=32, sample_weight=None, verbose=0, device=False):
         """keras Model.evaluate for the notebook's metrics (cell 2: metrics=[Jaccard, sparse_accuracy_ignoring_last_label]):
         returns [loss, Jaccard, accuracy].  The argmax mask and the per-image/per-class pixel counts are produced on

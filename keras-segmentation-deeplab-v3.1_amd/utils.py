@@ -114,6 +114,24 @@ def calculate_iou_multiscale(model, X, label, nb_classes=21, **tta_kwargs):
     return np.roll(plain, -1, axis=(0, 1)).astype(float)
 
 
+def calculate_iou_sliding(model, X, label, nb_classes=21, **slide_kwargs):
+    """calculate_iou with the masks of Model.predict_sliding: images of any size, each judged at its own
+    resolution; the same layout, rolled class 0 included.  X and label are arrays [N,Hi,Wi,3] / [N,Hi,Wi] or lists of images
+    / label maps of different sizes.  The masks come from the device; the matrix is calculate_iou_multiscale's host
+    bincount.  slide_kwargs: stride, blend, batch_size, pad_value."""
+    if "output" in slide_kwargs:
+        raise ValueError("calculate_iou_sliding builds its matrix from masks: output= is not an option")
+    masks = model.predict_sliding(X, output="mask", **slide_kwargs)
+    if len(masks) != len(label) or any(np.shape(m) != np.shape(l) for m, l in zip(masks, label)):
+        raise ValueError("calculate_iou_sliding: label must hold one [Hi,Wi] map per image")
+    pred = np.concatenate([np.asarray(m).reshape(-1) for m in masks]).astype(np.int64)
+    lab = np.concatenate([np.asarray(l).reshape(-1) for l in label]).astype(np.int64)
+    C = int(model.output.shape[-1])   # Model.confusion_matrix's extent: the model's classes
+    keep = (lab >= 0) & (lab < min(nb_classes, C))
+    plain = np.bincount(lab[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+    return np.roll(plain, -1, axis=(0, 1)).astype(float)
+
+
 def prepare_targets(labels, n_classes=21):
     """Device-side label half of SegmentationGenerator.__getitem__ (utils.py:375-402): raw label maps
     [B,H,W] or [B,HW] (uint8 / int32; numpy array or cuda tensor) -> (Y [B,HW,1], SW [B,HW]) cuda float32 tensors, ready

@@ -98,16 +98,22 @@ int dl3_dwconv3x3_bwd_sx(const float *g, const float *yraw, const float *cA, con
  * hipGraph keep what they were captured with); dl3_get_gemm_math returns the mode in effect (0 or 1) */
 int dl3_set_gemm_math(int mode);
 int dl3_get_gemm_math(void);
-/* P for the [M,K]x[K,N] GEMM's per-output-channel partials */
+/* The four queries below and dl3_pwconv_bwd_weight_splits are answers of the launch planner (csrc/pwplan.h) that every
+ * dl3_pwconv_* launch goes through: they describe the dispatch itself, not a restatement of it.
+ * P for the [M,K]x[K,N] GEMM's per-output-channel partials: the most rows any launch of that shape writes, over forward and
+ * bwd-data, one- and two-tensor operands, with and without mask / addend, aligned and unaligned operands, f32 and split
+ * math (plus the floors listed beside query_partials).  A launch that would write more rows than that returns DL3_EINVAL
+ * before anything runs. */
 int dl3_pwconv_partials(int M, int K, int N);
-/* which kernel a dl3_pwconv_fwd launch of this shape takes (16-byte aligned operands, leading dimensions multiples of 4,
- * no addend): 0 the tiled MFMA GEMM, 1 the weight-stationary streaming kernel of the HBM-bound layers (round 5: the
+/* which kernel a dl3_pwconv_fwd launch of this shape takes (dl3_pwconv_route dir 0: 16-byte aligned operands, rows back to
+ * back, no addend): 0 the tiled MFMA GEMM, 1 the weight-stationary streaming kernel of the HBM-bound layers (round 5: the
  * whole K x N matrix in LDS, every wave walks 32-row tiles on its own, 16-byte stores; deeplabv3p.py:175-198 at
  * 16..192 channels, M >= 32768), 2 the weight-stationary kernel of the MFMA-bound short reductions (round 6: K = 160 / 96 /
  * 64 into an output at least twice as wide, M >= 98304 forward / 65536 bwd-data, 131072 for K = 64; DL3_WS2=0 disables it — and its packed-output variant for the
  * logits layer, K = 256, N <= 32, ldy == N, M >= 8192; DL3_NARROW=0).  Diagnostic only. */
 int dl3_pwconv_fwd_impl(int M, int K, int N);
-/* ... and the route of a launch by name, for plans that want to assert what they benchmark (tests/test_host.py):
+/* ... and the route of a launch by name, for plans that want to assert what they benchmark (tests/test_host.py): the route
+ * of the planner's plan for the canonical operand form of each dir (16-byte aligned operands, rows back to back) —
  * dir 0 = forward (as dl3_pwconv_fwd_impl), 1 = bwd-data with the single-tensor dY, a mask operand and no addend, 2 = the
  * weight gradient (two-tensor operand), 3 = bwd-data with the single-tensor dY (rows back to back) and neither mask, addend
  * nor BatchNorm sums (the logits layer), 4 = the weight gradient with a single-tensor dY, folded by the launch (dw given),
@@ -148,6 +154,9 @@ int dl3_pwconv_bwd_data(const float *g, int ldg, const float *yraw, int ldyraw, 
                         const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
                         const float *dx_add, int ldadd, int add_div, float add_scale, const float *x_mean,
                         const float *x_invstd, float *dstat_partial, int M, int K, int N, void *stream);
+/* bytes of workspace a dl3_pwconv_bwd_weight* launch of this shape needs: the slabs and bias column-sum rows of the largest of
+ * the planner's plans over the launch's operand forms (two-tensor dY; single-tensor dY folded by the launch; single-tensor
+ * dY with the slabs left to the caller) */
 size_t dl3_pwconv_bwd_weight_workspace(int M, int K, int N);
 /* dw[K,N] = T(x)^T . dY ; dbias[N] (nullable) = colsum(dY).  The launch reduces over M in S =
  * dl3_pwconv_bwd_weight_splits(M, K, N, cA != NULL) deterministic slabs [S][K][N] at the head of the workspace and folds

@@ -21,31 +21,9 @@
 #include <vector>
 
 #include "common.h"
+#include "pwplan.h"  // GemmArgs, WgradArgs and the launch planner (host-only)
 
 namespace {
-
-struct GemmArgs {
-  const float *a; int lda;
-  const float *a2; int lda2;
-  const float *ka, *kb, *kc; int a_act;
-  const float *b; int ldb;
-  const float *bias;
-  float *c; int ldc;
-  int M, K, N;
-  const float *ep_x; int ld_epx;
-  const float *ep_scale, *ep_shift; int ep_act;
-  const float *ep_add; int ld_add; int add_div; float add_scale;
-  int stat_mode;  // 0 none, 1: sum c, sum c^2 ; 2: sum c, sum c*xhat
-  const float *ep_mean, *ep_invstd;
-  float *part;
-  int part_rows;  // rows the caller's partial buffer holds: the launch writes gridDim.y of them and zeroes the rest itself
-  int part_ld;    // columns per partial row (0: N) — a launch over a column slice of the output (run_gemm) writes into the whole matrix's rows
-  int mtiles;
-  const void *bp; int nsub;  // split math: weights pre-split into 3 bf16 planes in MFMA fragment order (pack_b_kernel)
-#ifdef DL3_PHASE_TIMING
-  long long *dbg;  // probe build (tools/r3/phase_probe.py): per-workgroup cycles in prologue / K loop / epilogue
-#endif
-};
 
 // probe builds only (-DDL3_PHASE_TIMING: build_variants/libdl3_timing.so, tools/r3/phase_probe.py)
 #ifdef DL3_PHASE_TIMING
@@ -56,9 +34,6 @@ long long *g_phase_dbg = nullptr;
 #endif
 
 constexpr int BK = 16;
-#ifndef DL3_STREAM_KMAX
-#define DL3_STREAM_KMAX 2048  // largest reduction depth the stream kernel takes (coefficient vectors in LDS)
-#endif
 #ifndef DL3_STREAM_KT_FWD
 #define DL3_STREAM_KT_FWD 16  // K-tile depth of the forward instantiation (32 measured in round 2: see DESIGN.md)
 #endif
@@ -67,15 +42,6 @@ constexpr int BK = 16;
 #endif
 #ifndef DL3_STREAM_PD_SMALL
 #define DL3_STREAM_PD_SMALL 2  // 32-row (small-M) stream kernels: K-tiles of operands in flight (register ring); 1 = the plain loop
-#endif
-#ifndef DL3_WGRAD_WGS_DEFAULT
-#define DL3_WGRAD_WGS_DEFAULT 1024
-#endif
-#ifndef DL3_GEMM_PY_DEFAULT
-#define DL3_GEMM_PY_DEFAULT 2048
-#endif
-#ifndef DL3_WGRAD_MS
-#define DL3_WGRAD_MS 16
 #endif
 
 
@@ -952,19 +918,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_stream_kernel(GemmArgs P) {
 // ---------------------------------------------------------------------------------------
 // weight gradient: dW[K,N] (+)= sum_m T(X)[m][k] * dY[m][n]; grid (ntn, ntk, S)
 // ---------------------------------------------------------------------------------------
-struct WgradArgs {
-  const float *x; int ldx;
-  const float *xs, *xt; int x_act;
-  const float *g; int ldg;
-  const float *y; int ldy;
-  const float *cA, *cB, *cC;
-  float *ws;  // [S][K][N]
-  int M, K, N, Mper;
-  float *dyout; int lddy;  // nullable: dY = cA*g + cB*y + cC written out [M][N] by the workgroups of the first K-tile row
-#ifdef DL3_PHASE_TIMING
-  long long *dbg;
-#endif
-};
+// (WgradArgs: csrc/pwplan.h)
 
 // VEC: 1 = 16-byte loads of x and of g / y, 0 = scalar loads of both, 2 (round 5) = 16-byte loads of x only (N = classes)
 template <int TA, int TB, int WA, int WB, int VEC, bool SPL = false>
@@ -1586,8 +1540,6 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const long long 
     if (c0 + i < cols && r0 + tx < rows) out[(size_t)(c0 + i) * rows + r0 + tx] = tile[tx][i];
 }
 
-
-int env_int(const char *name);
 
 // ---------------------------------------------------------------------------------------
 // round 5: weight-stationary streaming forward kernel for the HBM-bound layers
@@ -2537,16 +2489,6 @@ __global__ __launch_bounds__(256) void pw_ksplit32_kernel(GemmArgs P) {
   }
 }
 
-// shapes and row counts the K-split kernel takes: 1 024 - 16 384 rows
-inline int ksplit_tn(int M, int K, int N) {
-  // (a pure function of the shape: the answer sizes the statistic partial buffers when a plan is lowered — dl3_pwconv_partials —
-  // and picks the kernel at every launch; the DL3_KSPLIT / DL3_KSPLIT_ROWS knobs of round 5's A/B are gone)
-  if (M > 16384 || M < 1024 || K < 192 || K > DL3_STREAM_KMAX || K % 4 != 0 || N % 4 != 0) return 0;
-  const int tn = dl3_cdiv(N, 32);
-  // 64-, 96- and 160-wide outputs: the ones the 64-column-per-wave kernels pad (to 128, 128 and 256 columns)
-  return (tn == 2 || tn == 3 || tn == 5) ? tn : 0;
-}
-
 // ---- dl3_pwconv_fwd_rows: a handful of rows (the ASPP image-pooling branch: ONE row per image, deeplabv3p.py:375-382,
 // and its share of concat_projection, :402-406): Y[m][n] = act(ka*x + kc)[m][:] . W[:][n] + bias + addend, in DOUBLE.  The
 // result is a per-image constant the network adds to every pixel of the 64x64 map: its rounding error does not average
@@ -2591,180 +2533,9 @@ __global__ __launch_bounds__(256) void pw_rows_f64_kernel(GemmArgs P) {
   }
 }
 
-// the layer shapes the kernel is instantiated for (K, N) -> (KQ, TN); 0: not served
-struct WsShape { int K, TN; };
-inline int ws_tn(int K, int N) {
-  if (K % 8 != 0 || N % 4 != 0) return 0;
-  const int tn = dl3_cdiv(N, 32);
-  // MobileNetV2's HBM-bound 1x1 convolutions (alpha = 1): 32->16, 16->96, 96->24, 24->144, 144->24, 144->32, 32->192, 192->32
-  switch (K) {
-    case 16: return tn == 3 ? tn : 0;
-    case 24: return tn == 5 ? tn : 0;
-    case 32: return (tn == 1 || tn == 6) ? tn : 0;
-    case 96: return tn == 1 ? tn : 0;
-    case 144: return tn == 1 ? tn : 0;
-    case 192: return tn == 1 ? tn : 0;
-    default: return 0;
-  }
-}
-int ws_grid(int M) {
-  // persistent: three workgroups per CU, never more waves than 32-row tiles
-  const int tiles = dl3_cdiv(M, 32);
-  const int g = dl3_cdiv(tiles, 4);
-  return g < 768 ? g : 768;
-}
-#ifndef DL3_WS2_NW
-#define DL3_WS2_NW 8
-#endif
-// round 6: the weight-stationary kernel for MFMA-bound short reductions (pw_ws2_kernel): row groups per column tile — one
-// workgroup per CU over all column tiles
-int ws2_groups(int M, int ntn) {
-  const int tiles = dl3_cdiv(M, 32);
-  int g = 256 / ntn;
-  if (g < 1) g = 1;
-  const int cap = dl3_cdiv(tiles, DL3_WS2_NW);
-  return g < cap ? g : cap;
-}
-// shapes it takes: a reduction of 160, 96 or 64 (MobileNetV2's 64 x 64 blocks, deeplabv3p.py:175-198) into an output at least twice
-// as wide, from a row count below which a wave walks too few tiles to pay for loading its 60-100 KB weight slice — measured per
-// direction (profiles/r06_ab_calls.txt calls 34 / 35, tiled -> weight-stationary): forward 160 -> 960 at 65 536 rows 0.218 -> 0.228 ms,
-// at 98 304 0.339 -> 0.312; bwd-data 960 <- 160 at 32 768 rows 0.151 -> 0.158, at 65 536 0.295 -> 0.261 (the tiled kernel's masked
-// epilogue is the longer one); reduction 64: 131 072 rows either way.  DL3_WS2=0: the tiled stream kernel serves everything.
-bool ws2_shape(int M, int K, int N, bool bwd = false) {
-  static const int env = env_int("DL3_WS2");
-  if (env == 0) return false;
-  const int minrows = K == 64 ? 131072 : (bwd ? 65536 : 98304);
-  return M >= minrows && N % 4 == 0 && ((K == 160 && N >= 320) || (K == 96 && N >= 192) || (K == 64 && N >= 128));
-}
-inline int ws2_tn(int K) { return K == 160 ? 5 : (K == 96 ? 3 : 4); }
-// 1: forward, 2: bwd-data (single-tensor dY, mask and BatchNorm-backward sums from the forward input, no addend), 3: bwd-data
-// of the expand convolutions 64 -> 384 (two-tensor operand over a reduction of 384, 64-wide gradient, optional residual), 0: no
-int ws2_wanted(const GemmArgs &A, bool fwd, bool vec) {
-  static const int env = env_int("DL3_WS2");
-  if (env == 0 || !vec || (A.bias && !fwd) || A.ldc % 4 != 0 || (((uintptr_t)A.c) & 15) != 0) return 0;
-  if (!fwd && A.a2) {
-    if (A.M < 131072 || A.K != 384 || A.N != 64 || !A.ka || A.bias || A.stat_mode == 1 || !A.ep_x) return 0;
-    if (A.ld_epx % 4 != 0 || (((uintptr_t)A.ep_x) & 15) != 0) return 0;
-    if (A.ep_add && (A.add_div != 1 || A.ld_add % 4 != 0 || (((uintptr_t)A.ep_add) & 15) != 0)) return 0;
-    return 3;
-  }
-  if (A.ep_add || A.a2 || !ws2_shape(A.M, A.K, A.N, !fwd)) return 0;
-  if (fwd) return 1;
-  if (A.ka || !A.ep_x || A.ld_epx % 4 != 0 || (((uintptr_t)A.ep_x) & 15) != 0 || A.stat_mode == 1) return 0;
-  return 2;
-}
-
-// forward launch served by the weight-stationary kernel of the HBM-bound layers?
-bool ws_wanted(const GemmArgs &A, bool fwd, bool vec) {
-  if (!fwd || !vec || A.ep_add || A.a2) return false;
-  if (A.ldc % 4 != 0 || (((uintptr_t)A.c) & 15) != 0) return false;  // 16-byte stores
-  if (A.M < 32768) return false;
-  return ws_tn(A.K, A.N) != 0;
-}
-
-// round 6: the logits layer (N = classes <= 32 off a 256-wide input): 1 = forward with the packed narrow output (pw_ws2_kernel
-// FLAT), 2 = bwd-data over the narrow reduction (pw_narrowk_kernel), 0 = no.  DL3_NARROW=0: the tiled kernels (A/B aid).
-bool narrow_on() {
-  static const int env = env_int("DL3_NARROW");
-  return env != 0;
-}
-bool narrow_shape(int M, int K, int N) { return narrow_on() && M >= 8192 && K == 256 && N <= 32; }
-int narrow_wanted(const GemmArgs &A, bool fwd, bool avec) {
-  if (A.a2 || A.ep_add || A.M < 8192 || !narrow_on()) return 0;
-  if (fwd && avec && narrow_shape(A.M, A.K, A.N) && A.ldc == A.N && (((uintptr_t)A.c) & 15) == 0) return 1;
-  // (16 384 rows: measured 8 192 rows 0.011 -> 0.013 ms, 65 536 rows 0.039 -> 0.023)
-  if (A.M >= 16384 && A.K <= 32 && A.N == 256 && !A.ka && A.a_act == DL3_ACT_NONE && !A.ep_x && !A.bias && A.stat_mode == 0 && A.lda == A.K &&
-      A.ldc % 4 == 0 && ((((uintptr_t)A.a) | ((uintptr_t)A.c)) & 15) == 0)
-    return 2;
-  return 0;
-}
-int narrow_groups(int M) {
-  const int cap = dl3_cdiv(dl3_cdiv(M, 32), DL3_WS2_NW);
-  return cap < 256 ? cap : 256;
-}
-// ... and its weight gradient (pw_wgrad_narrow_kernel): slabs = workgroups, one per CU, never more waves than 16-row spans
-// (from 131 072 rows: at 65 536 the eight-wave meeting and the 256-slab fold cost what the loop saves, 0.053 -> 0.056 ms)
-bool wgrad_narrow_shape(int M, int K, int N) { return narrow_on() && M >= 131072 && K == 256 && N <= 32; }
-int wgrad_narrow_slabs(int M) {
-  const int cap = dl3_cdiv(dl3_cdiv(M, 16), DL3_WS2_NW);
-  return cap < 256 ? cap : 256;
-}
-
-// ---- configuration choice -------------------------------------------------------------
-struct GemmCfg { int id, BM, BN; };
-const GemmCfg kGemmCfgs[] = {{0, 128, 128}, {1, 256, 64}, {2, 256, 32}, {3, 128, 160}, {4, 128, 96},
-                             {5, 32, 256},  {6, 32, 128}};  // 5, 6: four waves side by side, for small M
-constexpr int kNumGemmCfgs = 7;
-
-int env_int(const char *name) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : -1;
-}
-
-// small: the 32-row configurations may be chosen (they exist for the stream kernel only)
-GemmCfg pick_gemm(int M, int K, int N, bool two, bool small, bool fwd = true) {
-  const int forced = env_int("DL3_GEMM_CFG");  // tuning aid (tools/gemm_tune.py)
-  if (forced >= 0 && forced < kNumGemmCfgs && (small || kGemmCfgs[forced].BM != 32)) return kGemmCfgs[forced];
-  // measured exception (tools/gemm_tune.py): a forward GEMM with a very short reduction and a wide output
-  // (24 -> 144 at 128x128) is a pure streaming kernel and wants the tall 256x64 tile
-  // (forward launches only: the single-tensor bwd-data launches of round 4 are `!two` as well — 144 <- 24 at 128x128 ran
-  // 0.71 -> 0.83 ms through this exception)
-  if (fwd && !two && K < 32 && N > 128 && M >= 65536) return kGemmCfgs[1];
-  double best = 1e30;
-  GemmCfg bc = kGemmCfgs[0];
-  for (const GemmCfg &c : kGemmCfgs) {
-    if (c.BM == 32 && !small) continue;
-    // measured on MI355X (tools/gemm_tune.py): ~80 TFLOP/s sustained fp32 MFMA, ~3 TB/s streaming; re-reads of A by
-    // the other column tiles of a row tile are L2 hits thanks to the XCD remap (charged at 1/4)
-    const double ntn = dl3_cdiv(N, c.BN), mp = (double)dl3_cdiv(M, c.BM) * c.BM;
-    // fewer workgroups than the chip holds (2 per CU) leave matrix pipes idle; the 32-row configs pay ~15 % more
-    // per MFMA (every wave re-reads the shared A rows through L1) and are for exactly that case
-    const double blocks = (double)dl3_cdiv(M, c.BM) * ntn;
-    const double util = blocks < 512.0 ? blocks / 512.0 : 1.0;
-    const double t_mfma = 2.0 * mp * K * ntn * c.BN / 80e12 / util * (c.BM == 32 ? 1.15 : 1.0);
-    const double t_mem = 4.0 * ((double)M * K * (1.0 + 0.25 * (ntn - 1)) * (two ? 2 : 1) + (double)M * N) / 3e12;
-    const double cost = (t_mfma > t_mem ? t_mfma : t_mem) + 0.25 * (t_mfma + t_mem);
-    if (cost < best) { best = cost; bc = c; }
-  }
-  return bc;
-}
-
-// masked bwd-data launch whose epilogue operand can be prefetched (pw_gemm_stream_kernel EPI 2)
-bool pre_ok(const GemmArgs &A) {
-  return A.ep_x && !A.bias && !A.ep_add && env_int("DL3_GEMM_PRE") != 0;
-}
-// ... and for which the 128x96 prefetching tile beats the cost model's choice: short reductions (the epilogue is as
-// long as the main loop) into a wide output made of whole 96-column tiles, with enough row tiles to fill the chip
-bool pre_wanted(const GemmArgs &A) {
-  return A.K <= 320 && A.N % 96 == 0 && A.N >= 2 * A.K && A.M >= 65536;
-}
-
-int gemm_grid_y(int M, int N, const GemmCfg &c, int K = 0) {
-  const int mtiles = dl3_cdiv(M, c.BM), ntn = dl3_cdiv(N, c.BN);
-  // target number of workgroups per launch (DL3_GEMM_PY overrides: tuning aid).  Measured on MI355X, whole step:
-  const int pytot = env_int("DL3_GEMM_PY");
-  // plenty of row tiles (>= 4 per resident workgroup): 512 workgroups = exactly two per CU, each a persistent loop over
-  // its row tiles (sweep at B=64: 256 -> 64.3 ms, 384 -> 66.4, 512 -> 57.7, 640 -> 63.0, 768 -> 60.3, 2048 -> 58.4: any
-  // count that is not a whole number of waves of the chip leaves a ragged last wave); fewer tiles: several waves of
-  // short workgroups balance better (B=2: 2048 -> 4.97 ms, 512 -> 5.08)
-  // round 6: ... and 5-16 LONG tiles per resident workgroup (reduction >= 512, at most 1 024 row tiles: Xception at B = 16 / 32)
-  // do not want the persistent loop either: a workgroup that walks 5 or 6 such tiles wastes up to a fifth of the launch on
-  // the quantisation, which the dispatcher's own balancing of one- or two-tile workgroups does not (same-call A/B, cfg4 B=16:
-  // 736 -> 736 forward 0.680 -> 0.630 ms, 1536 -> 1536 2.65 -> 2.46; 85.2 -> 87.4 img/s; MobileNetV2 B=16 / 128 unchanged / -0.5 %)
-  const long tiles = (long)mtiles * ntn;
-  const bool long_few = K >= 512 && mtiles <= 1024 && tiles < 8192;
-  const int dflt = long_few ? 4096 : (tiles >= 2048 ? 512 : DL3_GEMM_PY_DEFAULT);
-  int py = (pytot > 0 ? pytot : dflt) / ntn;
-  if (py < 32) py = 32;
-  if (mtiles <= py) return mtiles;
-  const int iters = dl3_cdiv(mtiles, py);  // every workgroup loops over the same number of row tiles ...
-  const int even = dl3_cdiv(mtiles, iters);
-  // ... unless that leaves more than a tenth of the chip's 512 slots empty (512 row tiles x 5 column tiles: 86 x 5 = 430
-  // workgroups of 6 tiles, most CUs carry 12 tile-times; 102 x 5 = 510 workgroups of 5 or 6 carry 10-11: the Xception
-  // 736 -> 736 GEMM at 65536 rows 0.810 -> 0.733 ms forward, 0.924 -> 0.869 bwd-data).
-  if ((long)even * ntn * 10 < 512L * 9) return py;
-  return even;
-}
+// ---- launches ------------------------------------------------------------------------------------
+// csrc/pwplan.h decides (route, instantiation, grid, LDS bytes, partial rows); launch_gemm / launch_wgrad hold the switch over the
+// template instantiations a plan names and nothing else: no shape test, no environment variable.
 
 // split math (opt-in): device scratch for the packed weights of the launch in flight, one buffer per DEVICE.  Launches on
 // one stream are ordered, so one buffer serves them all — split-math launches of a device must not be issued from two
@@ -2799,286 +2570,166 @@ void *pack_scratch(size_t bytes, hipStream_t st) {
   return nb;
 }
 
-int g_gemm_math = -1;  // DL3_MATH_ENV
-bool split_math() {
-  if (g_gemm_math >= 0) return g_gemm_math == 1;
-  const char *e = getenv("DL3_GEMM_MATH");  // "split": fp32 as 3 x bf16 on the bf16 matrix pipe; default: f32 MFMA
-  return e && e[0] == 's';
-}
-
-template <int TM, int TN, int WM, int WN>
-void launch_gemm(const GemmArgs &A, dim3 grid, hipStream_t st, int vec) {
-  // 16-byte loads on both operands (1), scalar loads on both (0: tiny GEMMs with K = number of classes), or on the
-  // activation operand only (2: N = number of classes — the logits layer's forward)
-  if (vec == 1) hipLaunchKernelGGL((pw_gemm_kernel<TM, TN, WM, WN, 1>), grid, dim3(256), 0, st, A);
-  else if (vec == 2) hipLaunchKernelGGL((pw_gemm_kernel<TM, TN, WM, WN, 2>), grid, dim3(256), 0, st, A);
-  else hipLaunchKernelGGL((pw_gemm_kernel<TM, TN, WM, WN, 0>), grid, dim3(256), 0, st, A);
-}
-
-inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-// returns the number of stat partial rows the launch writes (= grid.y)
-int run_gemm_one(GemmArgs A, hipStream_t st) {
-  const bool two = A.a2 != nullptr;
-  const bool avec = (A.K % 4 == 0) && (A.lda % 4 == 0) && al16(A.a) && (!two || ((A.lda2 % 4 == 0) && al16(A.a2)));
-  const bool bvec = (A.N % 4 == 0) && (A.ldb % 4 == 0) && al16(A.b);
-  const bool vec = avec && bvec;
-  const int vmode = vec ? 1 : (avec ? 2 : 0);
-  const bool stream = vec && A.K <= DL3_STREAM_KMAX;
-  // (a per-image addend stays on the forward instantiation when its straight-line epilogue can take it: 32-row blocks
-  // inside one image)
-  const bool fwd = !two && !A.ep_x && A.stat_mode != 2 && !(A.ep_add && A.add_div > 1 && A.add_div % 32 != 0);
-  if (const int nr = split_math() ? 0 : narrow_wanted(A, fwd, avec)) {
-    if (nr == 1) {
-      const int nrg = ws2_groups(A.M, 1);
-      hipLaunchKernelGGL((pw_ws2_kernel<32, 1, DL3_WS2_NW, false, false, false, true>), dim3(1, nrg), dim3(64 * DL3_WS2_NW), 0, st, A);
-      return nrg;
-    }
-    hipLaunchKernelGGL((pw_narrowk_kernel<8, DL3_WS2_NW>), dim3(narrow_groups(A.M), A.N / 256), dim3(64 * DL3_WS2_NW), 0, st, A);
-    return 0;
-  }
-  if (const int w2 = split_math() ? 0 : ws2_wanted(A, fwd, vec)) {
-    if (w2 == 3) {
-      const int nrg = ws2_groups(A.M, 1);
-      const dim3 grid(1, nrg);
-      if (A.ep_add) hipLaunchKernelGGL((pw_ws2_kernel<48, 2, DL3_WS2_NW, true, true, true>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-      else hipLaunchKernelGGL((pw_ws2_kernel<48, 2, DL3_WS2_NW, true, true, false>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-      return nrg;
-    }
-    const int tn = ws2_tn(A.K), ntn = dl3_cdiv(A.N, 32 * tn), nrg = ws2_groups(A.M, ntn);
-    if (w2 == 2) {
-      const dim3 grid(ntn, nrg);
-      if (A.K == 160) hipLaunchKernelGGL((pw_ws2_kernel<20, 5, DL3_WS2_NW, true>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-      else if (A.K == 96) hipLaunchKernelGGL((pw_ws2_kernel<12, 3, DL3_WS2_NW, true>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-      else hipLaunchKernelGGL((pw_ws2_kernel<8, 4, DL3_WS2_NW, true>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-      return nrg;
-    }
-    const dim3 grid(ntn, nrg), blk(512);
-    DL3_T(A.dbg = g_phase_dbg;)
-#ifndef DL3_WS2_NW
-#define DL3_WS2_NW 8
-#endif
-    if (A.K == 160) hipLaunchKernelGGL((pw_ws2_kernel<20, 5, DL3_WS2_NW>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-    else if (A.K == 96) hipLaunchKernelGGL((pw_ws2_kernel<12, 3, DL3_WS2_NW>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-    else hipLaunchKernelGGL((pw_ws2_kernel<8, 4, DL3_WS2_NW>), grid, dim3(64 * DL3_WS2_NW), 0, st, A);
-    return nrg;
-  }
-  if (ws_wanted(A, fwd, vec) && !split_math()) {
-    const dim3 grid(ws_grid(A.M)), blk(256);
-#define DL3_WS(KQ_, TN_, OC_) hipLaunchKernelGGL((pw_fwd_ws_kernel<KQ_, TN_, OC_>), grid, blk, 0, st, A)
-    const int tn = ws_tn(A.K, A.N);
-    // (workgroups per CU: the most the registers allow without spilling)
-    if (A.K == 16) DL3_WS(2, 3, 4);
-    else if (A.K == 24) DL3_WS(3, 5, 3);
-    else if (A.K == 32 && tn == 1) DL3_WS(4, 1, 4);
-    else if (A.K == 32) DL3_WS(4, 6, 3);
-    else if (A.K == 96) DL3_WS(12, 1, 4);
-    else if (A.K == 144) DL3_WS(18, 1, 3);
-    else DL3_WS(24, 1, 3);
-#undef DL3_WS
-    return (int)grid.x;
-  }
-  if (vec && !split_math()) {
-    const int ktn = ksplit_tn(A.M, A.K, A.N);
-    if (ktn) {
-      const dim3 grid(dl3_cdiv(A.M, 32)), blk(256);
-      if (ktn == 2) {
-        if (two) hipLaunchKernelGGL((pw_ksplit32_kernel<2, true>), grid, blk, 0, st, A);
-        else hipLaunchKernelGGL((pw_ksplit32_kernel<2, false>), grid, blk, 0, st, A);
-      } else if (ktn == 3) {
-        if (two) hipLaunchKernelGGL((pw_ksplit32_kernel<3, true>), grid, blk, 0, st, A);
-        else hipLaunchKernelGGL((pw_ksplit32_kernel<3, false>), grid, blk, 0, st, A);
-      } else {
-        if (two) hipLaunchKernelGGL((pw_ksplit32_kernel<5, true>), grid, blk, 0, st, A);
-        else hipLaunchKernelGGL((pw_ksplit32_kernel<5, false>), grid, blk, 0, st, A);
-      }
-      return (int)grid.x;
-    }
-  }
-  GemmCfg c = pick_gemm(A.M, A.K, A.N, two, stream, fwd);
-  if (stream && pre_ok(A) && pre_wanted(A)) c = kGemmCfgs[4];
-  A.mtiles = dl3_cdiv(A.M, c.BM);
+// one launch of the plan P over the operands A; -1: the split-math weight scratch is unavailable (nothing launched)
+int launch_gemm(GemmArgs A, const GemmPlan &P, hipStream_t st) {
+  constexpr int NW = DL3_WS2_NW;
+  const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256), blkw(64 * NW);
+  A.mtiles = P.mtiles;
   DL3_T(A.dbg = g_phase_dbg;)
-  dim3 grid(dl3_cdiv(A.N, c.BN), gemm_grid_y(A.M, A.N, c, A.K));
-  // stream-A kernel: 10-25 % faster than the LDS-staged kernel on every layer shape, forward and bwd-data
-  // (tools/gemm_tune.py).  The two-tensor bwd-data operand uses 16-deep K-tiles so that its register budget does not
-  // spill.  (Unaligned operands take the LDS-staged kernel below.)
-  if (stream) {
-    dim3 blk(256);
-    if (split_math() && c.id != 5 && c.id != 6) {  // (the 32-row small-M tiles keep the f32 MFMA: their split weight tiles exceed the LDS)
-      const unsigned dyn = 4u * (two ? 3 : 2) * (unsigned)dl3_cdiv(A.K, 32) * 32;
-      const int ktiles = dl3_cdiv(A.K, 32);
-      A.nsub = dl3_cdiv(A.N, 32);
-      const size_t pieces = (size_t)ktiles * 2 * 3 * A.nsub * 64;
-      void *ws = pack_scratch(pieces * 16, st);
-      if (!ws) return -1;
-      A.bp = ws;
-      hipLaunchKernelGGL(pack_b_kernel, dim3(dl3_cdiv(ktiles * 2 * A.nsub * 64, 256)), blk, 0, st, A.b, A.ldb, A.K, A.N,
-                         (u32x4 *)ws, ktiles, A.nsub);
-#define DL3_SPLIT(TM_, TN_, WN_)                                                                                     \
-  do {                                                                                                               \
-    if (two) hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, true, 32, 0, WN_, 1>), grid, blk, dyn, st, A);        \
-    else if (fwd) hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, false, 32, 1, WN_, 1>), grid, blk, dyn, st, A);  \
-    else hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, false, 32, 0, WN_, 1>), grid, blk, dyn, st, A);           \
-  } while (0)
-      if (c.id == 4 && pre_ok(A)) {
-        if (two) hipLaunchKernelGGL((pw_gemm_stream_kernel<1, 3, true, 32, 2, 1, 1>), grid, blk, dyn, st, A);
-        else hipLaunchKernelGGL((pw_gemm_stream_kernel<1, 3, false, 32, 2, 1, 1>), grid, blk, dyn, st, A);
-        return (int)grid.y;
+#define DL3_GO(KERNEL_, BLK_) hipLaunchKernelGGL((KERNEL_), grid, BLK_, P.lds, st, A)
+  switch (P.kernel) {
+    case PW_NARROW_FLAT: DL3_GO((pw_ws2_kernel<32, 1, NW, false, false, false, true>), blkw); return 0;
+    case PW_NARROWK: DL3_GO((pw_narrowk_kernel<8, NW>), blkw); return 0;
+    case PW_WS2:
+      if (P.two) {
+        if (P.add) DL3_GO((pw_ws2_kernel<48, 2, NW, true, true, true>), blkw);
+        else DL3_GO((pw_ws2_kernel<48, 2, NW, true, true, false>), blkw);
+      } else if (!P.fwd) {
+        switch (P.tn) {
+          case 5: DL3_GO((pw_ws2_kernel<20, 5, NW, true>), blkw); break;
+          case 3: DL3_GO((pw_ws2_kernel<12, 3, NW, true>), blkw); break;
+          default: DL3_GO((pw_ws2_kernel<8, 4, NW, true>), blkw); break;
+        }
+      } else {
+        switch (P.tn) {
+          case 5: DL3_GO((pw_ws2_kernel<20, 5, NW>), blkw); break;
+          case 3: DL3_GO((pw_ws2_kernel<12, 3, NW>), blkw); break;
+          default: DL3_GO((pw_ws2_kernel<8, 4, NW>), blkw); break;
+        }
       }
-      switch (c.id) {
-        case 0: DL3_SPLIT(1, 4, 1); break;
-        case 1: DL3_SPLIT(2, 2, 1); break;
-        case 2: DL3_SPLIT(2, 1, 1); break;
-        case 3: DL3_SPLIT(1, 5, 1); break;
-        default: DL3_SPLIT(1, 3, 1); break;
+      return 0;
+    case PW_WS:   // (KQ, TN, workgroups per CU: the most the registers allow without spilling)
+      switch (P.kq * 10 + P.tn) {
+        case 23: DL3_GO((pw_fwd_ws_kernel<2, 3, 4>), blk); break;
+        case 35: DL3_GO((pw_fwd_ws_kernel<3, 5, 3>), blk); break;
+        case 41: DL3_GO((pw_fwd_ws_kernel<4, 1, 4>), blk); break;
+        case 46: DL3_GO((pw_fwd_ws_kernel<4, 6, 3>), blk); break;
+        case 121: DL3_GO((pw_fwd_ws_kernel<12, 1, 4>), blk); break;
+        case 181: DL3_GO((pw_fwd_ws_kernel<18, 1, 3>), blk); break;
+        default: DL3_GO((pw_fwd_ws_kernel<24, 1, 3>), blk); break;
+      }
+      return 0;
+    case PW_KSPLIT:
+      switch (P.tn * 2 + (P.two ? 1 : 0)) {
+        case 4: DL3_GO((pw_ksplit32_kernel<2, false>), blk); break;
+        case 5: DL3_GO((pw_ksplit32_kernel<2, true>), blk); break;
+        case 6: DL3_GO((pw_ksplit32_kernel<3, false>), blk); break;
+        case 7: DL3_GO((pw_ksplit32_kernel<3, true>), blk); break;
+        case 10: DL3_GO((pw_ksplit32_kernel<5, false>), blk); break;
+        default: DL3_GO((pw_ksplit32_kernel<5, true>), blk); break;
+      }
+      return 0;
+    case PW_STREAM:
+      if (P.split) {
+        const int ktiles = dl3_cdiv(A.K, 32);
+        A.nsub = dl3_cdiv(A.N, 32);
+        const size_t pieces = (size_t)ktiles * 2 * 3 * A.nsub * 64;
+        void *ws = pack_scratch(pieces * 16, st);
+        if (!ws) return -1;
+        A.bp = ws;
+        hipLaunchKernelGGL(pack_b_kernel, dim3(dl3_cdiv(ktiles * 2 * A.nsub * 64, 256)), blk, 0, st, A.b, A.ldb, A.K, A.N,
+                           (u32x4 *)ws, ktiles, A.nsub);
+      }
+      // KT: 32-deep K-tiles in split math; the two-tensor bwd-data operand uses 16-deep ones so that its register budget does not spill
+#define DL3_STREAM(TM_, TN_, WN_, KT2_, KTF_, KTB_, MATH_)                                               \
+  do {                                                                                                  \
+    if (P.two) DL3_GO((pw_gemm_stream_kernel<TM_, TN_, true, KT2_, 0, WN_, MATH_>), blk);               \
+    else if (P.fwd) DL3_GO((pw_gemm_stream_kernel<TM_, TN_, false, KTF_, 1, WN_, MATH_>), blk);         \
+    else DL3_GO((pw_gemm_stream_kernel<TM_, TN_, false, KTB_, 0, WN_, MATH_>), blk);                    \
+  } while (0)
+#define DL3_F32(TM_, TN_, WN_) DL3_STREAM(TM_, TN_, WN_, 16, DL3_STREAM_KT_FWD, DL3_STREAM_KT_BWD1, 0)
+#define DL3_SPLIT(TM_, TN_, WN_) DL3_STREAM(TM_, TN_, WN_, 32, 32, 32, 1)
+      if (P.pre) {   // (cfg 4: the 128x96 tile with the prefetched mask operand)
+        if (P.split) {
+          if (P.two) DL3_GO((pw_gemm_stream_kernel<1, 3, true, 32, 2, 1, 1>), blk);
+          else DL3_GO((pw_gemm_stream_kernel<1, 3, false, 32, 2, 1, 1>), blk);
+        } else {
+          if (P.two) DL3_GO((pw_gemm_stream_kernel<1, 3, true, 16, 2, 1>), blk);
+          else DL3_GO((pw_gemm_stream_kernel<1, 3, false, 16, 2, 1>), blk);
+        }
+      } else if (P.split) {
+        switch (P.cfg) {
+          case 0: DL3_SPLIT(1, 4, 1); break;
+          case 1: DL3_SPLIT(2, 2, 1); break;
+          case 2: DL3_SPLIT(2, 1, 1); break;
+          case 3: DL3_SPLIT(1, 5, 1); break;
+          default: DL3_SPLIT(1, 3, 1); break;
+        }
+      } else {
+        switch (P.cfg) {
+          case 0: DL3_F32(1, 4, 1); break;
+          case 1: DL3_F32(2, 2, 1); break;
+          case 2: DL3_F32(2, 1, 1); break;
+          case 3: DL3_F32(1, 5, 1); break;
+          case 5: DL3_F32(1, 2, 4); break;
+          case 6: DL3_F32(1, 1, 4); break;
+          default: DL3_F32(1, 3, 1); break;
+        }
       }
 #undef DL3_SPLIT
-      return (int)grid.y;
-    }
-#define DL3_STREAM(TM_, TN_, WN_)                                                                                    \
-  do {                                                                                                               \
-    if (two) hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, true, 16, 0, WN_>), grid, blk, 0, st, A);           \
-    else if (fwd) hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, false, DL3_STREAM_KT_FWD, 1, WN_>), grid, blk, 0, st, A); \
-    else hipLaunchKernelGGL((pw_gemm_stream_kernel<TM_, TN_, false, DL3_STREAM_KT_BWD1, 0, WN_>), grid, blk, 0, st, A); \
-  } while (0)
-    if (c.id == 4 && pre_ok(A)) {
-      if (two) hipLaunchKernelGGL((pw_gemm_stream_kernel<1, 3, true, 16, 2, 1>), grid, blk, 0, st, A);
-      else hipLaunchKernelGGL((pw_gemm_stream_kernel<1, 3, false, 16, 2, 1>), grid, blk, 0, st, A);
-      return (int)grid.y;
-    }
-    switch (c.id) {
-      case 0: DL3_STREAM(1, 4, 1); break;
-      case 1: DL3_STREAM(2, 2, 1); break;
-      case 2: DL3_STREAM(2, 1, 1); break;
-      case 3: DL3_STREAM(1, 5, 1); break;
-      case 5: DL3_STREAM(1, 2, 4); break;
-      case 6: DL3_STREAM(1, 1, 4); break;
-      default: DL3_STREAM(1, 3, 1); break;
-    }
+#undef DL3_F32
 #undef DL3_STREAM
-    return (int)grid.y;
+      return 0;
+    case PW_LDS:
+#define DL3_LDS(TM_, TN_, WM_, WN_)                                                     \
+  do {                                                                                  \
+    if (P.vmode == 1) DL3_GO((pw_gemm_kernel<TM_, TN_, WM_, WN_, 1>), blk);             \
+    else if (P.vmode == 2) DL3_GO((pw_gemm_kernel<TM_, TN_, WM_, WN_, 2>), blk);        \
+    else DL3_GO((pw_gemm_kernel<TM_, TN_, WM_, WN_, 0>), blk);                          \
+  } while (0)
+      switch (P.cfg) {
+        case 0: DL3_LDS(2, 2, 2, 2); break;
+        case 1: DL3_LDS(2, 2, 4, 1); break;
+        case 2: DL3_LDS(2, 1, 4, 1); break;
+        case 3: DL3_LDS(1, 5, 4, 1); break;
+        default: DL3_LDS(1, 3, 4, 1); break;
+      }
+#undef DL3_LDS
+      return 0;
   }
-  switch (c.id) {
-    case 0: launch_gemm<2, 2, 2, 2>(A, grid, st, vmode); break;
-    case 1: launch_gemm<2, 2, 4, 1>(A, grid, st, vmode); break;
-    case 2: launch_gemm<2, 1, 4, 1>(A, grid, st, vmode); break;
-    case 3: launch_gemm<1, 5, 4, 1>(A, grid, st, vmode); break;
-    default: launch_gemm<1, 3, 4, 1>(A, grid, st, vmode); break;
+#undef DL3_GO
+  return 0;
+}
+
+// one weight-gradient launch of the plan P (cpart: the narrow kernel's column sums for the bias gradient, nullable)
+void launch_wgrad(const WgradArgs &A, const WgradPlan &P, float *cpart, hipStream_t st) {
+  const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256);
+  if (P.narrow) {
+    hipLaunchKernelGGL((pw_wgrad_narrow_kernel<2, DL3_WS2_NW>), grid, dim3(64 * DL3_WS2_NW), 0, st, A, cpart);
+    return;
   }
-  return (int)grid.y;
-}
-
-// round 6: Xception's 728-channel layers (deeplabv3p.py:300-306) are stored 736 wide — 23 column blocks of 32,
-// which no tile width divides: six 128-wide tiles compute 24 (the stream kernel multiplies zero weight columns like any other).
-// 23 = 2 x 4 + 3 x 5: such a launch is issued as TWO over disjoint column ranges of the same output, [0, N - 480) on the
-// 128-wide tiles and the last 480 columns on the 160-wide ones — 23 blocks exactly, both launches several full rounds of the
-// chip.  The operand rows are read by both (the second pass over a 65 536 x 736 operand is 0.19 GB against 0.65 ms of MFMA
-// time); partial sums land in disjoint columns of the same rows.  (First cut, 640 + 96 columns: the 128 x 96 tile of the
-// narrow launch costs 0.78 of a 128-wide one — forward 0.749 -> 0.712 ms, bwd-data 0.798 -> 0.796.)  DL3_COLSPLIT=0: one launch.
-constexpr int kColsplitTail = 480;
-bool colsplit_shape(int M, int K, int N) {
-  static const int env = env_int("DL3_COLSPLIT");
-  return env != 0 && M >= 32768 && K >= 256 && K <= DL3_STREAM_KMAX && N >= kColsplitTail + 128 && N % 128 == 96 && N % 160 != 0;
-}
-int run_gemm(GemmArgs A, hipStream_t st) {
-  const bool two = A.a2 != nullptr;
-  const bool vec = (A.K % 4 == 0) && (A.lda % 4 == 0) && al16(A.a) && (!two || ((A.lda2 % 4 == 0) && al16(A.a2))) &&
-                   (A.N % 4 == 0) && (A.ldb % 4 == 0) && al16(A.b);
-  // (single-tensor operand only: the two-tensor bwd-data form, which the engine does not use once the weight-gradient launch
-  // has written dY, came out 2 % slower in two launches — 0.834 -> 0.851 ms)
-  if (!vec || two || split_math() || !colsplit_shape(A.M, A.K, A.N)) return run_gemm_one(A, st);
-  const int n1 = A.N - kColsplitTail;
-  GemmArgs S[2] = {A, A};
-  S[0].N = n1;
-  S[1].N = kColsplitTail;
-  S[1].b += n1; S[1].c += n1;
-  if (A.bias) S[1].bias += n1;
-  if (A.ep_x) S[1].ep_x += n1;
-  if (A.ep_scale) { S[1].ep_scale += n1; S[1].ep_shift += n1; }
-  if (A.ep_mean) { S[1].ep_mean += n1; S[1].ep_invstd += n1; }
-  if (A.ep_add) S[1].ep_add += n1;
-  if (A.part) S[1].part += 2 * (size_t)n1;
-  int rows = 0;
-  for (GemmArgs &q : S) {
-    q.part_ld = A.N;
-    const int r = run_gemm_one(q, st);
-    if (r < 0) return r;
-    rows = r > rows ? r : rows;
+#define DL3_GO(KERNEL_) hipLaunchKernelGGL((KERNEL_), grid, blk, 0, st, A)
+  if (P.row) {   // (cfg 2 or 8, 16-byte loads on both operands: wgrad_row_ok)
+    if (P.cfg == 2) {
+      if (A.dyout) DL3_GO((pw_wgrad_row_kernel<5, 1, 1, 4, true>));
+      else DL3_GO((pw_wgrad_row_kernel<5, 1, 1, 4, false>));
+    } else {
+      if (A.dyout) DL3_GO((pw_wgrad_row_kernel<3, 1, 1, 4, true>));
+      else DL3_GO((pw_wgrad_row_kernel<3, 1, 1, 4, false>));
+    }
+    return;
   }
-  return rows;
-}
-
-struct WgCfg { int id, BKT, BNT; };
-const WgCfg kWgCfgs[] = {{0, 64, 64},  {1, 128, 128}, {2, 160, 128}, {3, 128, 160}, {4, 64, 128},
-                         {5, 128, 64}, {6, 32, 128},  {7, 128, 32},  {8, 96, 128},  {9, 128, 96}};
-
-// M splits the tile cost model reasons with: ~1024 workgroups, capped by slab traffic and by rows per split
-int wgrad_splits_model(int M, int K, int N, const WgCfg &c, int target = DL3_WGRAD_WGS_DEFAULT) {
-  const long tiles = (long)dl3_cdiv(K, c.BKT) * dl3_cdiv(N, c.BNT);
-  long S = target / tiles;
-  const long cap_traffic = (long)((double)M * (K + N) / (4.0 * K * N));
-  const long cap_rows = M / 64;
-  if (S > cap_traffic) S = cap_traffic;
-  if (S > cap_rows) S = cap_rows;
-  if (S < 1) S = 1;
-  return (int)S;
-}
-
-// ... and the M splits a launch gets.  Every split writes a K x N slab that the fold reads back; for the 160-wide tiles
-// on a small weight matrix (<= 160 x 960) at 32k-128k rows that is a fifth of the launch's bytes, and two workgroups per CU
-// (half the slabs) are faster.  Measured in situ (round 4, calls 16 / 17, B=16: M = 65536): 160 x 960 291 -> 258 us,
-// 960 x 160 253 -> 230, 576 x 160 180 -> 156; whole step 1 055 / 1 068 / 1 071 -> 1 068 / 1 082 / 1 086 img/s.  NOT a general
-// rule: the same halving on Xception's 736 x 736 at the same M costs 24 % of the launch, on 64 x 384 5 %, and at
-// M = 16384 (B=4) the 160-wide shapes lose 12 % (profiles/r04_ab_calls.txt, call 17).
-int wgrad_splits(int M, int K, int N, const WgCfg &c) {
-  const int S = wgrad_splits_model(M, K, N, c);
-  const bool wide = (c.id == 2 || c.id == 3) && (long)K * N <= 160L * 960 && M >= 32768;
-  if (wide && 2.0 * (double)S * K * N > 0.1 * (double)M * (K + N)) return wgrad_splits_model(M, K, N, c, DL3_WGRAD_WGS_DEFAULT / 2);
-  return S;
-}
-
-WgCfg pick_wgrad(int M, int K, int N, bool two) {
-  const int forced = env_int("DL3_WGRAD_CFG");
-  if (forced >= 0 && forced < 10) return kWgCfgs[forced];
-  // measured shortcuts (tools/gemm_tune.py, MI355X, M >= 32k rows): small weight matrices want the 64x64 tile (more
-  // workgroups per M split), 160-multiples want the 160-wide tiles so the big operand is read once
-  if (M >= 32768) {
-    if (K >= 32 && N >= 32 && (long)K * N <= 32768) return kWgCfgs[0];
-    if (N % 160 == 0 && K >= 128 && K % 160 != 0) return kWgCfgs[3];
-    if (K % 160 == 0 && K % 128 != 0 && N >= 128 && N % 160 != 0) return kWgCfgs[2];
-    if (K % 160 == 0 && N % 160 == 0 && K >= 320 && N >= 320) return kWgCfgs[3];
+#define DL3_WG(TA_, TB_, WA_, WB_)                                                            \
+  do {                                                                                        \
+    if (P.vec == 1 && P.split) DL3_GO((pw_wgrad_kernel<TA_, TB_, WA_, WB_, 1, true>));        \
+    else if (P.vec == 1) DL3_GO((pw_wgrad_kernel<TA_, TB_, WA_, WB_, 1>));                    \
+    else if (P.vec == 2) DL3_GO((pw_wgrad_kernel<TA_, TB_, WA_, WB_, 2>));                    \
+    else DL3_GO((pw_wgrad_kernel<TA_, TB_, WA_, WB_, 0>));                                    \
+  } while (0)
+  switch (P.cfg) {
+    case 0: DL3_WG(1, 1, 2, 2); break;
+    case 1: DL3_WG(2, 2, 2, 2); break;
+    case 2: DL3_WG(5, 1, 1, 4); break;
+    case 3: DL3_WG(1, 5, 4, 1); break;
+    case 4: DL3_WG(2, 1, 1, 4); break;
+    case 5: DL3_WG(1, 2, 4, 1); break;
+    case 6: DL3_WG(1, 1, 1, 4); break;
+    case 7: DL3_WG(1, 1, 4, 1); break;
+    case 8: DL3_WG(3, 1, 1, 4); break;
+    default: DL3_WG(1, 3, 4, 1); break;
   }
-  double best = 1e30;
-  WgCfg bc = kWgCfgs[0];
-  for (const WgCfg &c : kWgCfgs) {
-    const double ntk = dl3_cdiv(K, c.BKT), ntn = dl3_cdiv(N, c.BNT);
-    // few rows: the M split is capped (partial-slab traffic), so small tiles are what fills the chip
-    const double blocks = ntk * ntn * wgrad_splits_model(M, K, N, c);
-    const double util = blocks < 512.0 ? blocks / 512.0 : 1.0;
-    const double t_mfma = 2.0 * M * ntk * c.BKT * ntn * c.BNT / 80e12 / util;
-    const double t_mem = 4.0 * ((double)M * K * (1.0 + 0.25 * (ntn - 1)) +
-                                (double)M * N * (1.0 + 0.25 * (ntk - 1)) * (two ? 2 : 1)) / 3e12;
-    const double cost = (t_mfma > t_mem ? t_mfma : t_mem) + 0.25 * (t_mfma + t_mem);
-    if (cost < best) { best = cost; bc = c; }
-  }
-  return bc;
-}
-
-int colsum_rows(int M) {
-  int pr = M / 256;
-  if (pr < 1) pr = 1;
-  if (pr > 256) pr = 256;
-  return pr;
-}
-
-template <int TA, int TB, int WA, int WB>
-void launch_wgrad(const WgradArgs &A, dim3 grid, hipStream_t st, int vec) {
-  if (vec == 1 && split_math())
-    hipLaunchKernelGGL((pw_wgrad_kernel<TA, TB, WA, WB, 1, true>), grid, dim3(256), 0, st, A);
-  else if (vec == 1) hipLaunchKernelGGL((pw_wgrad_kernel<TA, TB, WA, WB, 1>), grid, dim3(256), 0, st, A);
-  else if (vec == 2) hipLaunchKernelGGL((pw_wgrad_kernel<TA, TB, WA, WB, 2>), grid, dim3(256), 0, st, A);
-  else hipLaunchKernelGGL((pw_wgrad_kernel<TA, TB, WA, WB, 0>), grid, dim3(256), 0, st, A);
+#undef DL3_WG
+#undef DL3_GO
 }
 
 }  // namespace
@@ -3100,88 +2751,13 @@ extern "C" int dl3_set_gemm_math(int mode) {
 
 extern "C" int dl3_get_gemm_math(void) { return split_math() ? 1 : 0; }
 
-extern "C" int dl3_pwconv_partials(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0) return 0;
-  // the stat partial row count must not depend on which operand form is used: take the max
-  int p = 0;
-  for (int two = 0; two < 2; two++)
-    for (int small = 0; small < 2; small++)
-      for (int fwd = 0; fwd < 2; fwd++) {
-        const int q = gemm_grid_y(M, N, pick_gemm(M, K, N, two != 0, small != 0, fwd != 0), K);
-        p = q > p ? q : p;
-      }
-  if (ws_tn(K, N)) {  // the weight-stationary forward kernel writes one row per workgroup
-    const int q = ws_grid(M);
-    p = q > p ? q : p;
-  }
-  if (ws2_shape(M, K, N, true)) {   // (the lower of the two directions' row thresholds)
-    const int q = ws2_groups(M, dl3_cdiv(N, 32 * ws2_tn(K)));
-    p = q > p ? q : p;
-  }
-  if (narrow_shape(M, K, N)) {   // (the logits layer's forward: one column tile)
-    const int q = ws2_groups(M, 1);
-    p = q > p ? q : p;
-  }
-  if (M >= 131072 && K == 384 && N == 64) {   // (the two-tensor bwd-data route of the expand convolutions: one column tile)
-    const int q = ws2_groups(M, 1);
-    p = q > p ? q : p;
-  }
-  if (ksplit_tn(M, K, N)) {  // the K-split kernel of the small batches: one row per 32-row tile
-    const int q = dl3_cdiv(M, 32);
-    p = q > p ? q : p;
-  }
-  if (colsplit_shape(M, K, N)) {   // (two launches over column slices: each sizes its own grid)
-    const int a = dl3_pwconv_partials(M, K, N - kColsplitTail), b = dl3_pwconv_partials(M, K, kColsplitTail);
-    p = a > p ? a : p;
-    p = b > p ? b : p;
-  }
-  if (N % 96 == 0) {  // the prefetching bwd-data variant overrides the choice with the 128x96 tile (run_gemm)
-    const int q = gemm_grid_y(M, N, kGemmCfgs[4], K);
-    p = q > p ? q : p;
-  }
-  return p;
-}
-
-extern "C" int dl3_pwconv_fwd_impl(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0) return 0;
-  GemmArgs A{};
-  A.M = M; A.K = K; A.N = N; A.ldc = N;
-  if (split_math()) return 0;
-  if (narrow_wanted(A, true, true) == 1) return 2;
-  if (ws2_wanted(A, true, true)) return 2;
-  return ws_wanted(A, true, true) ? 1 : 0;
-}
-
-// the weight gradient of a launch with tile configuration c takes the one-tile-row kernel (DL3_WGRAD_ROW=0: off — A/B aid)
-static bool wgrad_row_ok(const WgCfg &c, int M, int K, int N) {
-  static const int row_env = env_int("DL3_WGRAD_ROW");
-  return row_env != 0 && !split_math() && dl3_cdiv(K, c.BKT) == 1 && K % 4 == 0 && N % 4 == 0 && (c.id == 2 || c.id == 8) && M >= 32768;
-}
-
-extern "C" int dl3_pwconv_route(int dir, int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0 || split_math()) return DL3_ROUTE_TILED;
-  if (dir == 2) return wgrad_row_ok(pick_wgrad(M, K, N, true), M, K, N) ? DL3_ROUTE_WGRAD_ROW : DL3_ROUTE_TILED;
-  if (dir == 4) {   // (single-tensor dY, dw given: the launch folds its own slabs)
-    if (wgrad_narrow_shape(M, K, N)) return DL3_ROUTE_NARROW;
-    return wgrad_row_ok(pick_wgrad(M, K, N, false), M, K, N) ? DL3_ROUTE_WGRAD_ROW : DL3_ROUTE_TILED;
-  }
-  GemmArgs A{};
-  if (dir == 3) {   // bwd-data of a layer K -> N without a mask operand: reduces over N, K wide
-    A.M = M; A.K = N; A.N = K; A.ldc = K; A.lda = N;
-    return narrow_wanted(A, true, false) == 2 ? DL3_ROUTE_NARROW : DL3_ROUTE_TILED;
-  }
-  if (dir == 0) {
-    A.M = M; A.K = K; A.N = N; A.ldc = N;
-    if (narrow_wanted(A, true, true) == 1) return DL3_ROUTE_NARROW;
-    if (ws2_wanted(A, true, true)) return DL3_ROUTE_WS_MFMA;
-    if (ws_wanted(A, true, true)) return DL3_ROUTE_WS_HBM;
-  } else {
-    // bwd-data of a layer K -> N: the GEMM reduces over N and is K wide
-    A.M = M; A.K = N; A.N = K; A.ldc = K; A.ld_epx = K;
-    A.ep_x = reinterpret_cast<const float *>(uintptr_t(16));   // (an aligned mask operand is present: only its presence matters)
-    if (ws2_wanted(A, false, true) == 2) return DL3_ROUTE_WS_MFMA;
-  }
-  return ksplit_tn(A.M, A.K, A.N) ? DL3_ROUTE_KSPLIT : DL3_ROUTE_TILED;
+// the queries are the planner's answers for the operand forms include/dl3.h documents (csrc/pwplan.h, query_*)
+extern "C" int dl3_pwconv_partials(int M, int K, int N) { return query_partials(M, K, N); }
+extern "C" int dl3_pwconv_fwd_impl(int M, int K, int N) { return query_fwd_impl(M, K, N); }
+extern "C" int dl3_pwconv_route(int dir, int M, int K, int N) { return query_route(dir, M, K, N); }
+extern "C" size_t dl3_pwconv_bwd_weight_workspace(int M, int K, int N) { return query_wgrad_workspace(M, K, N); }
+extern "C" int dl3_pwconv_bwd_weight_splits(int M, int K, int N, int two_tensor_dy) {
+  return query_wgrad_splits(M, K, N, two_tensor_dy != 0);
 }
 
 static int gemm_common_check(const char *name, int M, int K, int N) {
@@ -3189,52 +2765,55 @@ static int gemm_common_check(const char *name, int M, int K, int N) {
   return DL3_OK;
 }
 
-extern "C" int dl3_pwconv_fwd(const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
-                              const float *w, const float *bias, float *y, int ldy, int M, int K, int N,
-                              float *stat_partial, void *stream) {
-  int rc = gemm_common_check("pwconv_fwd", M, K, N);
+// plans the call (one launch, or the two of a column split), refuses a plan that would write more statistic partial rows than
+// A.part_rows — before anything is launched — and launches it
+static int run_gemm(const char *name, const GemmArgs &A, void *stream) {
+  const GemmLaunch L = plan_gemm(A);
+  for (int i = 0; i < L.n; i++)
+    DL3_CHECK_ARG(!A.part || L.plan[i].rows <= A.part_rows,
+                  "%s: M=%d K=%d N=%d: the launch writes %d statistic partial rows, the buffer holds %d (dl3_pwconv_partials)", name,
+                  A.M, A.K, A.N, L.plan[i].rows, A.part_rows);
+  for (int i = 0; i < L.n; i++)
+    DL3_CHECK_ARG(launch_gemm(L.args[i], L.plan[i], (hipStream_t)stream) >= 0,
+                  "%s: split-math weight scratch unavailable (first launch inside a stream capture?)", name);
+  DL3_LAUNCH_CHECK(name);
+  return DL3_OK;
+}
+
+// dl3_pwconv_fwd (add == NULL) and dl3_pwconv_fwd_add
+static int pwconv_fwd(const char *name, const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
+                      const float *w, const float *bias, float *y, int ldy, int M, int K, int N, float *stat_partial,
+                      bool with_add, const float *add, int ldadd, int add_div, void *stream) {
+  int rc = gemm_common_check(name, M, K, N);
   if (rc) return rc;
-  DL3_CHECK_ARG(x && w && y, "pwconv_fwd: null pointer");
-  DL3_CHECK_ARG(ldx >= K && ldy >= N, "pwconv_fwd: leading dimension too small");
-  DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "pwconv_fwd: scale/shift must come together");
+  DL3_CHECK_ARG(x && w && y && (add || !with_add), "%s: null pointer", name);
+  DL3_CHECK_ARG(ldx >= K && ldy >= N && (!with_add || (ldadd >= N && add_div >= 1)),
+                with_add ? "%s: bad leading dimension / add_div" : "%s: leading dimension too small", name);
+  DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "%s: scale/shift must come together", name);
   GemmArgs A{};
   A.a = x; A.lda = ldx; A.a2 = nullptr; A.lda2 = 0;
   A.ka = in_scale; A.kb = nullptr; A.kc = in_shift; A.a_act = in_act;
   A.b = w; A.ldb = N; A.bias = bias; A.c = y; A.ldc = ldy;
   A.M = M; A.K = K; A.N = N;
-  A.add_div = 1; A.add_scale = 1.f;
+  A.ep_add = add; A.ld_add = with_add ? ldadd : 0; A.add_div = with_add ? add_div : 1; A.add_scale = 1.f;
   A.stat_mode = stat_partial ? 1 : 0;
   A.part = stat_partial;
   A.part_rows = stat_partial ? dl3_pwconv_partials(M, K, N) : 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int written = run_gemm(A, st);
-  DL3_CHECK_ARG(written >= 0, "pwconv_fwd: split-math weight scratch unavailable (first launch inside a stream capture?)");
-  DL3_LAUNCH_CHECK("pwconv_fwd");
-  return DL3_OK;
+  return run_gemm(name, A, stream);
+}
+
+extern "C" int dl3_pwconv_fwd(const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
+                              const float *w, const float *bias, float *y, int ldy, int M, int K, int N,
+                              float *stat_partial, void *stream) {
+  return pwconv_fwd("pwconv_fwd", x, ldx, in_scale, in_shift, in_act, w, bias, y, ldy, M, K, N, stat_partial, false, nullptr, 0, 1,
+                    stream);
 }
 
 extern "C" int dl3_pwconv_fwd_add(const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
                                   const float *w, const float *bias, float *y, int ldy, int M, int K, int N,
                                   float *stat_partial, const float *add, int ldadd, int add_div, void *stream) {
-  int rc = gemm_common_check("pwconv_fwd_add", M, K, N);
-  if (rc) return rc;
-  DL3_CHECK_ARG(x && w && y && add, "pwconv_fwd_add: null pointer");
-  DL3_CHECK_ARG(ldx >= K && ldy >= N && ldadd >= N && add_div >= 1, "pwconv_fwd_add: bad leading dimension / add_div");
-  DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "pwconv_fwd_add: scale/shift must come together");
-  GemmArgs A{};
-  A.a = x; A.lda = ldx; A.a2 = nullptr; A.lda2 = 0;
-  A.ka = in_scale; A.kb = nullptr; A.kc = in_shift; A.a_act = in_act;
-  A.b = w; A.ldb = N; A.bias = bias; A.c = y; A.ldc = ldy;
-  A.M = M; A.K = K; A.N = N;
-  A.ep_add = add; A.ld_add = ldadd; A.add_div = add_div; A.add_scale = 1.f;
-  A.stat_mode = stat_partial ? 1 : 0;
-  A.part = stat_partial;
-  A.part_rows = stat_partial ? dl3_pwconv_partials(M, K, N) : 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int written = run_gemm(A, st);
-  DL3_CHECK_ARG(written >= 0, "pwconv_fwd_add: split-math weight scratch unavailable (first launch inside a stream capture?)");
-  DL3_LAUNCH_CHECK("pwconv_fwd_add");
-  return DL3_OK;
+  return pwconv_fwd("pwconv_fwd_add", x, ldx, in_scale, in_shift, in_act, w, bias, y, ldy, M, K, N, stat_partial, true, add, ldadd,
+                    add_div, stream);
 }
 
 extern "C" int dl3_pwconv_fwd_rows(const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
@@ -3284,57 +2863,7 @@ extern "C" int dl3_pwconv_bwd_data(const float *g, int ldg, const float *yraw, i
   A.ep_mean = x_mean; A.ep_invstd = x_invstd;
   A.part = dstat_partial;
   A.part_rows = dstat_partial ? dl3_pwconv_partials(M, N, K) : 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int written = run_gemm(A, st);
-  DL3_CHECK_ARG(written >= 0, "pwconv_bwd_data: split-math weight scratch unavailable (first launch inside a stream capture?)");
-  DL3_LAUNCH_CHECK("pwconv_bwd_data");
-  return DL3_OK;
-}
-
-extern "C" size_t dl3_pwconv_bwd_weight_workspace(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0) return 0;
-  // S depends on the operand form; size for the larger
-  const WgCfg c1 = pick_wgrad(M, K, N, false), c2 = pick_wgrad(M, K, N, true);
-  int S1 = wgrad_splits(M, K, N, c1), S2 = wgrad_splits(M, K, N, c2);
-  int S = S1 > S2 ? S1 : S2, crows = colsum_rows(M);
-  if (wgrad_narrow_shape(M, K, N)) {   // (one slab and one row of column sums per workgroup)
-    const int Sn = wgrad_narrow_slabs(M);
-    S = Sn > S ? Sn : S;
-    crows = Sn > crows ? Sn : crows;
-  }
-  return ((size_t)S * K * N + (size_t)crows * N) * sizeof(float);
-}
-
-extern "C" int dl3_pwconv_bwd_weight_splits(int M, int K, int N, int two_tensor_dy) {
-  if (M <= 0 || K <= 0 || N <= 0) return 0;
-  return wgrad_splits(M, K, N, pick_wgrad(M, K, N, two_tensor_dy != 0));
-}
-
-// one weight-gradient launch on tile configuration c (row: K fits one tile row of it — the straight-line kernel of the
-// expand convolutions, with the requests in front of the dY stores)
-static void launch_wgrad_cfg(const WgradArgs &A, const WgCfg &c, dim3 grid, hipStream_t st, int vec, bool row) {
-  if (row) {   // (c.id 2 or 8, 16-byte loads on both operands: wgrad_row_ok)
-    if (c.id == 2) {
-      if (A.dyout) hipLaunchKernelGGL((pw_wgrad_row_kernel<5, 1, 1, 4, true>), grid, dim3(256), 0, st, A);
-      else hipLaunchKernelGGL((pw_wgrad_row_kernel<5, 1, 1, 4, false>), grid, dim3(256), 0, st, A);
-    } else {
-      if (A.dyout) hipLaunchKernelGGL((pw_wgrad_row_kernel<3, 1, 1, 4, true>), grid, dim3(256), 0, st, A);
-      else hipLaunchKernelGGL((pw_wgrad_row_kernel<3, 1, 1, 4, false>), grid, dim3(256), 0, st, A);
-    }
-    return;
-  }
-  switch (c.id) {
-    case 0: launch_wgrad<1, 1, 2, 2>(A, grid, st, vec); break;
-    case 1: launch_wgrad<2, 2, 2, 2>(A, grid, st, vec); break;
-    case 2: launch_wgrad<5, 1, 1, 4>(A, grid, st, vec); break;
-    case 3: launch_wgrad<1, 5, 4, 1>(A, grid, st, vec); break;
-    case 4: launch_wgrad<2, 1, 1, 4>(A, grid, st, vec); break;
-    case 5: launch_wgrad<1, 2, 4, 1>(A, grid, st, vec); break;
-    case 6: launch_wgrad<1, 1, 1, 4>(A, grid, st, vec); break;
-    case 7: launch_wgrad<1, 1, 4, 1>(A, grid, st, vec); break;
-    case 8: launch_wgrad<3, 1, 1, 4>(A, grid, st, vec); break;
-    default: launch_wgrad<1, 3, 4, 1>(A, grid, st, vec); break;
-  }
+  return run_gemm("pwconv_bwd_data", A, stream);
 }
 
 static int pwconv_bwd_weight_impl(const float *x, int ldx, const float *in_scale, const float *in_shift,
@@ -3357,8 +2886,9 @@ static int pwconv_bwd_weight_impl(const float *x, int ldx, const float *in_scale
     return DL3_EWORKSPACE;
   }
   const bool two = cA != nullptr;
-  const WgCfg c = pick_wgrad(M, K, N, two);
-  const int S = wgrad_splits(M, K, N, c);
+  const bool xvec = (K % 4 == 0) && (ldx % 4 == 0) && al16(x);
+  const bool dvec = (N % 4 == 0) && (ldg % 4 == 0) && al16(g) && (!two || ((ldyraw % 4 == 0) && al16(yraw)));
+  const WgradPlan P = plan_wgrad(M, K, N, two, xvec, dvec, dy_out != nullptr, dw != nullptr);
   WgradArgs A{};
   A.x = x; A.ldx = ldx; A.xs = in_scale; A.xt = in_shift; A.x_act = in_act;
   A.g = g; A.ldg = ldg; A.y = two ? yraw : nullptr; A.ldy = ldyraw;
@@ -3366,36 +2896,20 @@ static int pwconv_bwd_weight_impl(const float *x, int ldx, const float *in_scale
   A.ws = (float *)workspace;
   A.M = M; A.K = K; A.N = N;
   A.dyout = dy_out; A.lddy = lddy;
-  A.Mper = dl3_cdiv(dl3_cdiv(M, S), DL3_WGRAD_MS) * DL3_WGRAD_MS;
+  A.Mper = P.Mper;
   DL3_T(A.dbg = g_phase_dbg;)
   hipStream_t st = (hipStream_t)stream;
-  dim3 grid(dl3_cdiv(N, c.BNT), dl3_cdiv(K, c.BKT), S);
-  const bool xvec = (K % 4 == 0) && (ldx % 4 == 0) && al16(x);
-  const bool dvec = (N % 4 == 0) && (ldg % 4 == 0) && al16(g) && (!two || ((ldyraw % 4 == 0) && al16(yraw)));
-  // the logits layer: N = classes, the whole K x N gradient in every wave's accumulators
-  if (xvec && !two && !dy_out && dw && !split_math() && wgrad_narrow_shape(M, K, N)) {
-    const int Sn = wgrad_narrow_slabs(M);
-    float *cpart = dbias ? A.ws + (size_t)Sn * K * N : nullptr;
-    hipLaunchKernelGGL((pw_wgrad_narrow_kernel<2, DL3_WS2_NW>), dim3(Sn), dim3(64 * DL3_WS2_NW), 0, st, A, cpart);
-    DL3_LAUNCH_CHECK("pwconv_bwd_weight(narrow)");
-    rc = dl3_reduce_partials(A.ws, Sn, K * N, dw, stream);
-    if (rc || !dbias) return rc;
-    return dl3_reduce_partials(cpart, Sn, N, dbias, stream);
-  }
-  launch_wgrad_cfg(A, c, grid, st, (xvec && dvec) ? 1 : (xvec ? 2 : 0), xvec && dvec && wgrad_row_ok(c, M, K, N));
-  DL3_LAUNCH_CHECK("pwconv_bwd_weight");
+  float *cpart = dbias ? A.ws + (size_t)P.slabs * K * N : nullptr;   // the column sums of the bias gradient, behind the slabs
+  launch_wgrad(A, P, cpart, st);
+  DL3_LAUNCH_CHECK(P.narrow ? "pwconv_bwd_weight(narrow)" : "pwconv_bwd_weight");
   if (!dw) return DL3_OK;  // the caller folds the [S][K][N] slabs itself (dl3_reduce_partials / _batched)
-  rc = dl3_reduce_partials(A.ws, S, K * N, dw, stream);
-  if (rc) return rc;
-  if (dbias) {
-    float *cpart = A.ws + (size_t)S * K * N;
-    const int pr = colsum_rows(M);
-    hipLaunchKernelGGL(colsum_kernel, dim3(dl3_cdiv(N, 64), pr), dim3(256), 0, st, g, ldg, M, N, cpart);
+  rc = dl3_reduce_partials(A.ws, P.slabs, K * N, dw, stream);
+  if (rc || !dbias) return rc;
+  if (!P.narrow) {   // (the narrow kernel wrote its column sums itself)
+    hipLaunchKernelGGL(colsum_kernel, dim3(dl3_cdiv(N, 64), P.colsum_rows), dim3(256), 0, st, g, ldg, M, N, cpart);
     DL3_LAUNCH_CHECK("pwconv_bwd_weight(colsum)");
-    rc = dl3_reduce_partials(cpart, pr, N, dbias, stream);
-    if (rc) return rc;
   }
-  return DL3_OK;
+  return dl3_reduce_partials(cpart, P.colsum_rows, N, dbias, stream);
 }
 
 extern "C" int dl3_pwconv_bwd_weight(const float *x, int ldx, const float *in_scale, const float *in_shift,

@@ -271,7 +271,8 @@ PW_CASES = [
 
 
 @pytest.mark.parametrize("case", PW_CASES)
-def test_pwconv_fwd(L, case):
+def test_pwconv_fwd(L, case, part_alloc=None):
+    """part_alloc (P, N) -> the [P][N][2] statistic partial buffer, for a caller that owns the memory around it"""
     M, K, N, lxe, lye, bias, act = case[:7]
     form = case[7] if len(case) > 7 else None
     rng = np.random.default_rng(3)
@@ -285,7 +286,7 @@ def test_pwconv_fwd(L, case):
     ref = xin @ w.astype(np.float64) + (b if bias else 0)
     P = L.dl3_pwconv_partials(M, K, N)
     yfull = torch.zeros(M, ldy, dtype=torch.float32, device="cuda")
-    part = empty(P, N, 2)
+    part = part_alloc(P, N) if part_alloc else empty(P, N, 2)
     xd = dev(xfull)
     call("dl3_pwconv_fwd", ptr(xd, xoff), ldx, ptr(dev(s)) if s is not None else None,
          ptr(dev(t)) if t is not None else None, a, ptr(dev(w)), ptr(dev(b)) if bias else None, ptr(yfull, lye), ldy,
@@ -420,10 +421,10 @@ def _place(a, off=0, extra=0):
     return dev(full), off + C + extra
 
 
-def _bwd_data(L, M, K, N, act, two, addmode, stats, form=None, lay=None):
+def _bwd_data(L, M, K, N, act, two, addmode, stats, form=None, lay=None, part_alloc=None):
     """dl3_pwconv_bwd_data against float64.  lay: {operand: (column offset, extra leading-dimension width)} for "x", "g"
     (yraw shares its layout) and "dx" (the addend shares it; dx lands in a NaN-filled buffer whose other columns must stay
-    NaN) — the strided operands the engine passes (views into concat buffers)"""
+    NaN) — the strided operands the engine passes (views into concat buffers).  part_alloc: as in test_pwconv_fwd"""
     lay = lay or {}
     (xo, xe), (go, ge), (do, de) = lay.get("x", (0, 0)), lay.get("g", (0, 0)), lay.get("dx", (0, 0))
     rng = np.random.default_rng(4)
@@ -452,7 +453,7 @@ def _bwd_data(L, M, K, N, act, two, addmode, stats, form=None, lay=None):
     assert np.array_equal(host(wT), w.T)
     P = L.dl3_pwconv_partials(M, N, K)
     lddx = do + K + de
-    dxb, dpart = empty(M, lddx), empty(P, K, 2)
+    dxb, dpart = empty(M, lddx), (part_alloc(P, K) if part_alloc else empty(P, K, 2))
     need_x = a != 0 or stats
     gd, ldg = _place(g, go, ge)
     yd, _ = _place(yraw, go, ge) if two else (None, 0)
@@ -722,6 +723,63 @@ def test_pwconv_column_split_23_blocks(L, M, K, N):
     test_pwconv_bwd_data(L, (M, N, K, 1, True, 1, True))     # (the GEMM's output width is the layer's K)
     test_pwconv_bwd_data(L, (M, N, K, 2, False, 0, True))
     test_pwconv_bwd_data(L, (M, N, K, None, False, 2, False))
+
+
+GUARD_ROWS = 4096           # more rows than any grid of these kernels writes: an overrun lands in memory the test owns
+GUARD_BITS = 0x7FA5C3E1     # a quiet-NaN bit pattern no kernel produces
+
+
+class _GuardedPartials:
+    """the statistic partial buffer of a launch as P rows followed by GUARD_ROWS guard rows, all filled with GUARD_BITS"""
+
+    def __call__(self, P, C):
+        self.P = P
+        self.full = empty(P + GUARD_ROWS, C, 2)
+        self.full.view(torch.int32).fill_(GUARD_BITS)
+        return self.full[:P]
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        return bool((self.full[self.P:].view(torch.int32) == GUARD_BITS).all())
+
+
+R_ANY = None   # (a launch form dl3_pwconv_route has no dir for)
+GUARD_FWD = [
+    # forward with BatchNorm sums — the smallest shape on each route: name, PW_CASES tuple, route of dir 0
+    ("lds-unaligned", (300, 30, 21, 0, 0, True, None), 0),
+    ("stream-tile", (1024, 160, 960, 0, 0, False, 2), 0),
+    ("ksplit", (1024, 960, 160, 0, 0, False, 2), 3),
+    ("ws-hbm", (32768, 16, 96, 0, 0, False, 2), 1),
+    ("ws-mfma-160", (98304, 160, 320, 0, 0, False, 2), 2),
+    ("ws-mfma-64", (131072, 64, 128, 0, 0, False, 2), 2),
+    ("packed-logits", (8192, 256, 21, 0, 0, True, 1), 5),
+    ("column-split", (32768, 256, 608, 0, 0, False, 1), 0),
+]
+GUARD_BWD = [
+    # bwd-data with BatchNorm-backward sums, the layer's (M, K, N): name, BD_CASES tuple, route of dir 1
+    ("ws-mfma-masked", (65536, 320, 160, 2, False, 0, True), 2),
+    ("ws-mfma-two-tensor-residual", (131072, 64, 384, 2, True, 1, True), R_ANY),
+    ("prefetch-128x96", (65536, 96, 48, 2, False, 0, True), 0),
+    ("column-split", (32768, 608, 256, 1, False, 0, True), 0),
+]
+
+
+@pytest.mark.parametrize("bwd,case,route", [pytest.param(False, c, r, id="fwd-" + n) for n, c, r in GUARD_FWD] +
+                         [pytest.param(True, c, r, id="bwd-" + n) for n, c, r in GUARD_BWD])
+def test_pwconv_partials_guard_band(L, bwd, case, route):
+    """no launch writes a statistic partial row past the dl3_pwconv_partials rows its caller allocates: behind the P rows lie
+    GUARD_ROWS rows of a sentinel bit pattern, which every route must leave bit-for-bit untouched while rows [0, P) fold to the
+    float64 sums (the asserts of test_pwconv_fwd / _bwd_data, on the guarded buffer)"""
+    M, K, N = case[:3]
+    if route is not R_ANY:
+        assert L.dl3_pwconv_route(1 if bwd else 0, M, K, N) == route
+    guard = _GuardedPartials()
+    if bwd:
+        _bwd_data(L, *case, part_alloc=guard)
+    else:
+        test_pwconv_fwd(L, case, part_alloc=guard)
+    assert guard.P == (L.dl3_pwconv_partials(M, N, K) if bwd else L.dl3_pwconv_partials(M, K, N))
+    assert guard.untouched()
 
 
 FUSED_CASES = [

@@ -664,3 +664,57 @@ def test_benchmarked_plan_lowers_consistently_without_a_gpu(monkeypatch):
     # Xception OS=8: no fused launches (no layer small enough), dY materialised for its 1x1 convolutions
     e5, c5 = _dry_engine(monkeypatch, "xception", 1, size=256, OS=8)
     assert c5["dl3_pwconv_bwd_fused"] == 0 and c5["dl3_pwconv_bwd_weight_dy"] > 50
+
+
+def _plan_table_tool():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("pwconv_plan_table", os.path.join(root, "tools", "pwconv_plan_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_pwconv_plan_table_equals_the_recorded_one():
+    """every answer of the 1x1-convolution planner's queries (route dir 0-4, fwd_impl, partial rows both ways, weight-gradient
+    workspace and splits) for the 1 102 recorded shapes — every 1x1 launch of the MobileNetV2 / Subpixel / Xception plans, every
+    shape of the op tests, each route family's (K, N) pairs around its row thresholds — equals
+    tests/golden/pwconv_plan_table.json, recorded from the library before csrc/pwplan.h replaced the hand-kept copies of the
+    dispatch (tools/pwconv_plan_table.py)"""
+    import json
+    T = _plan_table_tool()
+    gold = json.load(open(T.GOLDEN))
+    assert gold["fields"] == T.FIELDS and len(gold["rows"]) > 1000
+    rows = T.rows_for([r[:3] for r in gold["rows"]])
+    bad = [(g, r) for g, r in zip(gold["rows"], rows) if g != r]
+    assert not bad, "%d of %d shapes differ, first (recorded, now): %s" % (len(bad), len(rows), bad[:3])
+
+
+def test_pwconv_plan_table_under_the_knobs(tmp_path):
+    """... and under DL3_WS2=0, DL3_NARROW=0, DL3_COLSPLIT=0, DL3_WGRAD_ROW=0, DL3_GEMM_CFG=0..6 and DL3_GEMM_MATH=split, each in a
+    fresh process (four of them are read once per process), over the shapes of the benchmarked B=128 and B=2 plans"""
+    import json
+    T = _plan_table_tool()
+    gold = json.load(open(T.GOLDEN_KNOBS))
+    assert gold["fields"] == T.FIELDS and list(gold["rows"]) == T.KNOB_SETTINGS
+    for setting, want in gold["rows"].items():
+        rows = T.knob_rows(setting, [r[:3] for r in want], str(tmp_path / "shapes.json"))
+        bad = [(g, r) for g, r in zip(want, rows) if g != r]
+        assert len(rows) == len(want) and not bad, "%s: %d shapes differ, first (recorded, now): %s" % (setting, len(bad), bad[:3])
+
+
+def test_pwplan_header_is_host_only():
+    """csrc/pwplan.h — the planner every launch and every sizing query goes through — compiles alone with the host compiler: no
+    HIP type, no device call"""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    hdr = os.path.join(root, "keras-segmentation-deeplab-v3.1_amd", "csrc", "pwplan.h")
+    res = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-x", "c++", hdr], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    text = open(hdr).read()
+    assert "hip/" not in text and "hipStream" not in text and "malloc" not in text.lower()

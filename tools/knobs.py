@@ -43,6 +43,9 @@ KNOBS = {
     "DL3_WGRAD_ROW": ("1", "A/B", "0: the expand convolutions' weight gradient on the tiled kernel (round 6, call 18)"),
 }
 
+# headers that are one translation unit's own: their knobs are read at that unit
+PART_OF = {"csrc/pwplan.h": "csrc/pwgemm.hip"}
+
 
 def scan():
     found = {}
@@ -53,6 +56,7 @@ def scan():
         for i, line in enumerate(open(f, errors="ignore"), 1):
             for m in PAT.finditer(line):
                 site = os.path.relpath(f, ROOT).replace("keras-segmentation-deeplab-v3.1_amd/", "")
+                site = PART_OF.get(site, site)
                 sites = found.setdefault(m.group(1) or m.group(2), [])
                 if site not in sites:   # (files, not lines: the table must not go stale with every edit)
                     sites.append(site)

@@ -37,6 +37,7 @@ void dl3_set_error(const char *fmt, ...);
   } while (0)
 
 static inline int dl3_cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------- device helpers
 // Branch-free activation: act is wave-uniform, so the clamp bounds are scalar selects and the activation is

@@ -3,7 +3,7 @@
 // written as the planar U[B][C][N] that dl3_crf_inference reads.  Three input forms, the ones of evaltail.hip:
 //   plain     x [B][N][C]            materialised logits, or probabilities (is_prob)
 //   bilinear  logits_lo [B][Hi][Wi][C] -> the TF1 legacy bilinear resize in registers, bit-identical to
-//             dl3_resize_bilinear_fwd (its kernel's own contraction is pinned with __fmul_rn / __fmaf_rn / __fsub_rn)
+//             dl3_resize_bilinear_fwd (tailmath.h: the fused weight .w)
 //   shuffle   u [B][H][W][C*r*r]     -> Subpixel._phase_shift by index
 // One kernel: a workgroup owns 256 consecutive pixels of one image, a lane one pixel with its C <= 32 scores in
 // registers.  Consecutive lanes own consecutive pixels, so class c of a wave is one 256-byte run of plane c; where N is a
@@ -13,7 +13,7 @@
 // Arithmetic: subtract-max, expf and the sum in fp32; the quotient, scale, clip and the logarithm in double, rounded to
 // fp32 once (the form the accuracy test of tests/test_gpu_crf_unary.py asks for: see DESIGN.md §9).  -log, clip and
 // scale are monotone, so the arg-min of U is the first-maximum argmax of the scores unless the clip ties them.
-#include "common.h"
+#include "tailmath.h"
 
 namespace {
 
@@ -26,23 +26,6 @@ struct Geom {
   int a, b, c, d;     // bilinear: Hi, Wi, Ho, Wo; shuffle: H, W, r, -
   float sy, sx;       // bilinear: Hi / Ho, Wi / Wo
 };
-
-// dl3_resize_bilinear_fwd's source coordinates and weight as its kernel executes them (evaltail.hip, tf1_lerp .w): the
-// coordinate a rounded product, the weight ONE fused multiply-subtract
-struct Lerp {
-  int lo, hi;
-  float w;
-};
-__device__ __forceinline__ Lerp tf1_lerp(int o, float scale, int in_size) {
-  const float f = __fmul_rn((float)o, scale);
-  Lerp r;
-  r.lo = (int)floorf(f);
-  if (r.lo > in_size - 1) r.lo = in_size - 1;
-  r.hi = min(r.lo + 1, in_size - 1);
-  r.w = __fmaf_rn((float)o, scale, -(float)r.lo);
-  return r;
-}
-__device__ __forceinline__ float lerp1(float a, float b, float w) { return __fmaf_rn(__fsub_rn(b, a), w, a); }
 
 // scores of one pixel -> its unary energies, in place
 template <int MAXC>
@@ -115,10 +98,7 @@ __global__ __launch_bounds__(kPix) void crf_unary_kernel(const float *__restrict
     const float *tl = xb + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = xb + ((size_t)ly.lo * Wi + lx.hi) * C;
     const float *bl = xb + ((size_t)ly.hi * Wi + lx.lo) * C, *br = xb + ((size_t)ly.hi * Wi + lx.hi) * C;
 #pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      const int cc = min(c, C - 1);
-      z[c] = lerp1(lerp1(tl[cc], tr[cc], lx.w), lerp1(bl[cc], br[cc], lx.w), ly.w);
-    }
+    for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.w, ly.w);
   } else {
     // out[n, ia*r+q, ib*r+p, ch] = u[n, ia, ib, ch*r*r + p*r + q]  (dl3_phase_shift)
     const int H = g.a, W = g.b, r = g.c, rr = r * r;
@@ -151,8 +131,6 @@ __global__ __launch_bounds__(kPix) void crf_unary_kernel(const float *__restrict
     if (j < npix) st4(Ub + (size_t)c * N + i0 + j, ld4(smem + c * kPix + j));
   }
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int FORM>
 int launch(const char *who, const float *x, float *U, int B, int N, int C, Geom g, int is_prob, float scale, float clip,

@@ -9,7 +9,7 @@
 // order in double by a second launch — no float atomics, two runs are bit-identical.  Integer counts: a per-workgroup
 // LDS histogram (LDS integer atomics), then ONE global integer atomic per non-zero bin per workgroup — integer sums do
 // not depend on arrival order.
-#include "common.h"
+#include "tailmath.h"
 
 namespace {
 
@@ -18,32 +18,8 @@ constexpr int kFusedMaxC = 32;     // logits of a pixel in registers
 constexpr int kBand = 8;           // output rows per workgroup (bilinear form)
 constexpr int kStageBytes = 48 * 1024;
 
-// tf.image.resize_bilinear(align_corners=False) of TF 1.x, as in misc.hip: src = dst * (in/out), no half-pixel offset.
-// Every floating-point step is pinned (no contraction left to the compiler) to what dl3_resize_bilinear_fwd's kernel
-// executes: the source coordinate is a rounded product (it feeds floor), the fractional weight is ONE fused
-// multiply-subtract o * scale - lo (the compiler contracts `f - lo` there), and each lerp is a rounded difference
-// followed by one fused multiply-add.
-// wl: the weight as TF 1.x (and the oracle) state it, src - lower with src the ROUNDED product.  The resize kernel's
-// fused form differs from it by up to an ulp of src (2e-6 at 33 -> 513): the mask has to reproduce the kernel bit for
-// bit, the loss follows the stated formula — its logits are interpolated with wl (same source pixels, same lerps).
-struct Lerp {
-  int lo, hi;
-  float w, wl;
-};
-__device__ __forceinline__ Lerp tf1_lerp(int o, float scale, int in_size) {
-  const float f = __fmul_rn((float)o, scale);
-  Lerp r;
-  r.lo = (int)floorf(f);
-  if (r.lo > in_size - 1) r.lo = in_size - 1;
-  r.hi = min(r.lo + 1, in_size - 1);
-  r.w = __fmaf_rn((float)o, scale, -(float)r.lo);
-  r.wl = __fsub_rn(f, (float)r.lo);
-  return r;
-}
-// a + (b - a) * w the way dl3_resize_bilinear_fwd's kernel is compiled: the difference rounded, then ONE fused
-// multiply-add
-__device__ __forceinline__ float lerp1(float a, float b, float w) { return __fmaf_rn(__fsub_rn(b, a), w, a); }
-
+// (the bilinear form's weights, tailmath.h: the MASK has to reproduce dl3_resize_bilinear_fwd bit for bit and takes .w, the
+// loss follows the formula TF states — its logits are interpolated with .wl)
 // a lane's running sums.  The loss terms are fp32 values; they are ADDED in double (one v_fma_f64 per pixel), so that
 // what is left of the result's error is the per-pixel arithmetic alone and not the order of a float32 summation
 struct Acc {
@@ -193,10 +169,10 @@ __global__ __launch_bounds__(256) void eval_bilinear_kernel(const float *__restr
         for (int c = 0; c < MAXC; c++) {
           const int cc = min(c, C - 1);
           const float a0 = tl[cc], a1 = tr[cc], b0 = bl[cc], b1 = br[cc];
-          const float zm = lerp1(lerp1(a0, a1, lx.w), lerp1(b0, b1, lx.w), ly.w);   // dl3_resize_bilinear_fwd's value
+          const float zm = bilerp(a0, a1, b0, b1, lx.w, ly.w);   // dl3_resize_bilinear_fwd's value
           if (c == 0) mmx = zm;
           else if (c < C && zm > mmx) { mmx = zm; am = c; }
-          z[c] = lerp1(lerp1(a0, a1, lx.wl), lerp1(b0, b1, lx.wl), ly.wl);
+          z[c] = bilerp(a0, a1, b0, b1, lx.wl, ly.wl);
         }
         mk[k] = eval_pixel<MAXC>(z, C, lab[k], wt[k], a, hist, conf != nullptr, am);
       }
@@ -226,9 +202,10 @@ __global__ __launch_bounds__(256) void eval_shuffle_kernel(const float *__restri
                                                            long long *__restrict__ conf, int *__restrict__ mask, int H,
                                                            int W, int C, int r, int PB) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int rr = r * r, P = C * rr, LP = C * (rr + 1);
+  const SubpixelTile T(C, r);
+  const int rr = T.rr, P = T.P;
   float *tile = smem;                                   // [PB][C][rr + 1]
-  int *hist = reinterpret_cast<int *>(smem + PB * LP);
+  int *hist = reinterpret_cast<int *>(smem + PB * T.LP);
   const int n = blockIdx.y;
   const int wblocks = (W + PB - 1) / PB;
   const int ia = blockIdx.x / wblocks, ib0 = (blockIdx.x - ia * wblocks) * PB;
@@ -236,11 +213,7 @@ __global__ __launch_bounds__(256) void eval_shuffle_kernel(const float *__restri
   const int nh = 3 * C + (conf ? C * C : 0);
   for (int i = threadIdx.x; i < nh; i += 256) hist[i] = 0;
   const float *srcp = u + (((size_t)n * H + ia) * W + ib0) * P;
-  for (int t = threadIdx.x; t < pb * P; t += 256) {
-    const int px = t / P, e = t - px * P;
-    const int ch = e / rr, pq = e - ch * rr;
-    tile[px * LP + ch * (rr + 1) + pq] = srcp[t];
-  }
+  for (int t = threadIdx.x; t < pb * P; t += 256) { const int k = T.flat_cell(t); tile[k] = srcp[t]; }
   __syncthreads();
   Acc a = {0.0, 0};
   const int run = pb * r;   // shuffled pixels of the tile along one image row
@@ -249,7 +222,7 @@ __global__ __launch_bounds__(256) void eval_shuffle_kernel(const float *__restri
     const int q = idx / run, v = idx - q * run;
     const int px = v / r, p = v - px * r;
     const size_t m = ((size_t)n * H * r + (size_t)ia * r + q) * Wr + (size_t)ib0 * r + v;
-    const float *tp = tile + px * LP + p * r + q;
+    const float *tp = tile + T.cell(px, p * r + q);
     float z[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; c++) z[c] = tp[min(c, C - 1) * (rr + 1)];
@@ -319,15 +292,8 @@ __global__ __launch_bounds__(64) void eval_fold_kernel(const double *__restrict_
 
 inline int hist_ints(int C, bool conf) { return 3 * C + (conf ? C * C : 0); }
 
-inline int shuffle_pb(int W, int C, int r) {
-  const int per = C * (r * r + 1) * 4;
-  int pb = kStageBytes / per;
-  if (pb > W) pb = W;
-  // no more than ~1024 shuffled pixels per workgroup: enough workgroups per image to fill the device
-  const int cap = (1024 + r * r - 1) / (r * r);
-  if (pb > cap) pb = cap;
-  return pb;
-}
+// no more than ~1024 shuffled pixels per workgroup: enough workgroups per image to fill the device
+inline int shuffle_pb(int W, int C, int r) { return subpixel_tile_pixels(W, C, r, (1024 + r * r - 1) / (r * r)); }
 
 inline int plain_chunks(int HW) {
   int c = dl3_cdiv(HW, 256 * 4);
@@ -335,8 +301,6 @@ inline int plain_chunks(int HW) {
   if (c > 256) c = 256;
   return c;
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int check_common(const char *who, const void *x, const void *labels, const void *partials, const void *loss_sum,
                  const void *nnz, const void *counts, int N, int C, int maxc) {

@@ -2,7 +2,7 @@
 // :439; utils.py:190), Subpixel phase shift (subpixel.py:77-88), softmax (deeplabv3p.py:441,:444),
 // sparse_crossentropy_ignoring_last_label with temporal sample weights (utils.py:127-130) and argmax.
 // All HBM-bound, one pass each; backward kernels are gather-form (no atomics, deterministic).
-#include "common.h"
+#include "tailmath.h"
 
 namespace {
 
@@ -16,22 +16,7 @@ __device__ __forceinline__ float dl3_clip_pass(float q) { return (q >= 1e-7f && 
 // non-zero -> every term is zero anyway)
 #define DL3_NNZ_FLOOR 1e-20f
 
-// tf.image.resize_bilinear(align_corners=False) of TF 1.x: src = dst * (in/out), no half-pixel
-// offset; lower = floor(src), upper = min(lower+1, in-1), lerp = src - lower.
-struct Lerp {
-  int lo, hi;
-  float w;
-};
-__device__ __forceinline__ Lerp tf1_lerp(int o, float scale, int in_size) {
-  const float f = (float)o * scale;
-  Lerp r;
-  r.lo = (int)floorf(f);
-  if (r.lo > in_size - 1) r.lo = in_size - 1;
-  r.hi = min(r.lo + 1, in_size - 1);
-  r.w = f - (float)r.lo;
-  return r;
-}
-
+// (the TF1-legacy bilinear weights and lerps: tailmath.h; the resize kernels take the fused weight .w)
 __global__ __launch_bounds__(256) void resize_fwd_kernel(const float *__restrict__ x, int ldx,
                                                          const float *__restrict__ sc,
                                                          const float *__restrict__ sh, int act,
@@ -52,9 +37,7 @@ __global__ __launch_bounds__(256) void resize_fwd_kernel(const float *__restrict
     const float tr = dl3_act(es * r0[(size_t)lx.hi * ldx + c] + et, act);
     const float bl = dl3_act(es * r1[(size_t)lx.lo * ldx + c] + et, act);
     const float br = dl3_act(es * r1[(size_t)lx.hi * ldx + c] + et, act);
-    const float top = tl + (tr - tl) * lx.w;
-    const float bot = bl + (br - bl) * lx.w;
-    yo[(size_t)ox * ldy + c] = top + (bot - top) * ly.w;
+    yo[(size_t)ox * ldy + c] = bilerp(tl, tr, bl, br, lx.w, ly.w);
   }
 }
 
@@ -218,8 +201,8 @@ __global__ __launch_bounds__(256) void shuffle_xent_kernel(const float *__restri
                                                            float *__restrict__ loss_part, int H, int W, int C, int r,
                                                            int PB) {
   extern __shared__ float tile[];
-  __shared__ float red[4];
-  const int rr = r * r, P = C * rr, LP = C * (rr + 1);
+  const SubpixelTile T(C, r);
+  const int rr = T.rr, P = T.P;
   const int wblocks = (W + PB - 1) / PB;
   const int ib0 = (blockIdx.x % wblocks) * PB;
   const long row = blockIdx.x / wblocks;  // n * H + ia
@@ -227,17 +210,14 @@ __global__ __launch_bounds__(256) void shuffle_xent_kernel(const float *__restri
   const long n = row / H;
   const int pb = min(PB, W - ib0);
   const size_t flat = ((size_t)row * W + ib0) * P;
-  for (int t = threadIdx.x; t < pb * P; t += 256) {
-    const int px = t / P, e = t % P;
-    tile[px * LP + (e / rr) * (rr + 1) + e % rr] = u[flat + t];
-  }
+  for (int t = threadIdx.x; t < pb * P; t += 256) { const int k = T.flat_cell(t); tile[k] = u[flat + t]; }
   __syncthreads();
   const float inv_nnz = 1.f / fmaxf(*nnz, DL3_NNZ_FLOOR);
   const int Wr = W * r;
   float lsum = 0.f;
   for (int o = threadIdx.x; o < pb * rr; o += 256) {
     const int px = o / rr, pq = o % rr, pp = pq / r, q = pq % r;
-    float *cell = tile + px * LP + pq;
+    float *cell = tile + T.cell(px, pq);
     float z[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; c++) z[c] = cell[min(c, C - 1) * (rr + 1)];
@@ -274,14 +254,8 @@ __global__ __launch_bounds__(256) void shuffle_xent_kernel(const float *__restri
       if (c < C) cell[c * (rr + 1)] = (z[c] - (c == t ? 1.f : 0.f)) * gs;
   }
   __syncthreads();
-  for (int t = threadIdx.x; t < pb * P; t += 256) {
-    const int px = t / P, e = t % P;
-    du[flat + t] = tile[px * LP + (e / rr) * (rr + 1) + e % rr];
-  }
-  lsum = wave_sum(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  for (int t = threadIdx.x; t < pb * P; t += 256) { const int k = T.flat_cell(t); du[flat + t] = tile[k]; }
+  block_loss_partial(wave_sum(lsum), loss_part);
 }
 
 // k x k taps of T(x) side by side (Subpixel with kernel_size > 1): one thread per (output pixel, tap, channel)
@@ -378,7 +352,6 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *__restri
                                                            const float *__restrict__ nnz, float *__restrict__ probs,
                                                            float *__restrict__ dl, float *__restrict__ loss_part,
                                                            long M, int C) {
-  __shared__ float red[4];
   const float inv_nnz = 1.f / fmaxf(*nnz, DL3_NNZ_FLOOR);
   float lsum = 0.f;
   for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
@@ -412,10 +385,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *__restri
       for (int c = 0; c < C; c++) dl[(size_t)m * C + c] = (expf(r[c] - mx) * inv - (c == t ? 1.f : 0.f)) * gs;
     }
   }
-  lsum = wave_sum(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_loss_partial(wave_sum(lsum), loss_part);
 }
 
 // Loss tail, one pass over HBM.  Thread = pixel, logits held in registers (C <= 32); dlogits (and probs) leave
@@ -430,7 +400,6 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
                                                      int C, int Hi, int Wi, int Ho, int Wo, float sy, float sx) {
   constexpr int MAXC = 32;
   __shared__ float tile[256 * MAXC];
-  __shared__ float red[4];
   const float inv_nnz = 1.f / fmaxf(*nnz, DL3_NNZ_FLOOR);
   float lsum = 0.f;
   for (long base = (long)blockIdx.x * 256; base < M; base += (long)gridDim.x * 256) {
@@ -447,12 +416,7 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
       const float *tl = b + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = b + ((size_t)ly.lo * Wi + lx.hi) * C;
       const float *bl = b + ((size_t)ly.hi * Wi + lx.lo) * C, *br = b + ((size_t)ly.hi * Wi + lx.hi) * C;
 #pragma unroll
-      for (int c = 0; c < MAXC; c++) {
-        const int cc = min(c, C - 1);
-        const float top = tl[cc] + (tr[cc] - tl[cc]) * lx.w;
-        const float bot = bl[cc] + (br[cc] - bl[cc]) * lx.w;
-        z[c] = top + (bot - top) * ly.w;
-      }
+      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.wl, ly.wl);  // the weight TF states
     } else {
       // coalesced copy of the workgroup's 256 x C logits through LDS, then one row per thread (stride C is odd for
       // C = 21: conflict-free)
@@ -508,10 +472,7 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
       __syncthreads();
     }
   }
-  lsum = wave_sum(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_loss_partial(wave_sum(lsum), loss_part);
 }
 
 #ifndef XENT_PS
@@ -534,7 +495,6 @@ __global__ __launch_bounds__(256, 2) void xent32_fold_kernel(const float *__rest
                                                           float *__restrict__ loss_part, int N, int C, int Hi, int Wi,
                                                           int Ho, int Wo, float sy, float sx) {
   extern __shared__ __attribute__((aligned(16))) float fold_tile[];  // [Wo][C] dlogits of the row, [2][Wi][C] source rows, [Wo] x lerp table
-  __shared__ float red[4];
   float *src = fold_tile + (size_t)Wo * C;
   float *xw = src + 2 * (size_t)Wi * C;  // fractional x weight of every output column
   int *xlo = (int *)(xw + Wo);           // its lower source column
@@ -598,12 +558,7 @@ __global__ __launch_bounds__(256, 2) void xent32_fold_kernel(const float *__rest
       const float *bl = src + (Wi + lx.lo) * C, *br = src + (Wi + lx.hi) * C;
       float z[MAXC];
 #pragma unroll
-      for (int c = 0; c < MAXC; c++) {
-        const int cc = min(c, C - 1);
-        const float top = tl[cc] + (tr[cc] - tl[cc]) * lx.w;
-        const float bot = bl[cc] + (br[cc] - bl[cc]) * lx.w;
-        z[c] = top + (bot - top) * ly.w;
-      }
+      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.w, ly.w);  // the resize kernels' weight
       float mx = z[0];
 #pragma unroll
       for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
@@ -675,10 +630,7 @@ __global__ __launch_bounds__(256, 2) void xent32_fold_kernel(const float *__rest
     }
     __syncthreads();
   }
-  lsum = wave_sum(lsum);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_loss_partial(wave_sum(lsum), loss_part);
 }
 
 inline int ew_blocks(size_t n) {
@@ -751,11 +703,8 @@ extern "C" int dl3_resize_bilinear_bwd_rows(const float *xfold, float *dx, int l
 extern "C" int dl3_phase_shift(const float *in, float *out, int N, int H, int W, int Cout, int r, int inverse,
                                void *stream) {
   DL3_CHECK_ARG(in && out && N > 0 && H > 0 && W > 0 && Cout > 0 && r > 0, "phase_shift: bad argument");
-  // pixels per workgroup: as many as fit 48 KB of LDS (three workgroups per CU), at most 8
   const size_t per_px = (size_t)Cout * (r * r + 1) * sizeof(float);
-  int PB = (int)((48u << 10) / per_px);
-  if (PB > 8) PB = 8;
-  if (PB > W) PB = W;
+  const int PB = subpixel_tile_pixels(W, Cout, r, 8);
   const long blocks = (long)N * H * dl3_cdiv(W, PB > 0 ? PB : 1);
   if (PB >= 1 && blocks < (1L << 31)) {
     hipLaunchKernelGGL(phase_shift_lds_kernel, dim3((unsigned)blocks), dim3(256), PB * per_px, (hipStream_t)stream, in,
@@ -768,17 +717,9 @@ extern "C" int dl3_phase_shift(const float *in, float *out, int N, int H, int W,
   return DL3_OK;
 }
 
-static int shuffle_xent_pb(int W, int C, int r) {
-  const size_t per_px = (size_t)C * (r * r + 1) * sizeof(float);
-  int PB = (int)((48u << 10) / per_px);
-  if (PB > 8) PB = 8;
-  if (PB > W) PB = W;
-  return PB;
-}
-
 extern "C" int dl3_shuffle_xent_partials(int N, int H, int W, int C, int r) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || r <= 0) return 0;
-  const int PB = shuffle_xent_pb(W, C, r);
+  const int PB = subpixel_tile_pixels(W, C, r, 8);
   if (PB < 1) return 0;
   const long blocks = (long)N * H * dl3_cdiv(W, PB);
   return blocks < (1L << 30) ? (int)blocks : 0;
@@ -792,7 +733,7 @@ extern "C" int dl3_shuffle_softmax_xent(const float *u, const float *labels, con
   DL3_UNSUPPORTED(C > 32, "shuffle_softmax_xent: C=%d > 32 (use phase_shift + softmax_xent)", C);
   const int P = dl3_shuffle_xent_partials(N, H, W, C, r);
   DL3_UNSUPPORTED(P <= 0, "shuffle_softmax_xent: a pixel of %d x %d x %d floats does not fit the LDS tile", C, r, r);
-  const int PB = shuffle_xent_pb(W, C, r);
+  const int PB = subpixel_tile_pixels(W, C, r, 8);
   const size_t lds = (size_t)PB * C * (r * r + 1) * sizeof(float);
   if (C <= 24)
     hipLaunchKernelGGL(shuffle_xent_kernel<24>, dim3(P), dim3(256), lds, (hipStream_t)stream, u, labels, weights, nnz, du,
@@ -903,7 +844,7 @@ extern "C" int dl3_upsample_softmax_xent_fold(const float *logits_lo, const floa
   const char *pe = getenv("DL3_XENT_PREF");  // 0 = every row requests its own operands (tuning / test aid)
   // (float4 requests and LDS stores: source rows of whole float4s, 16-byte aligned; the source tile starts Wo * C floats in)
   const bool pref = (long)Wi * C <= 256L * XENT_PS && Wo <= 256 * XENT_PP && (Wi * C) % 4 == 0 && ((long)Wo * C) % 4 == 0 &&
-                    (((uintptr_t)logits_lo) & 15) == 0 && !(pe && atoi(pe) == 0);
+                    aligned16(logits_lo) && !(pe && atoi(pe) == 0);
 #define DL3_XENT(MAXC_, PREF_)                                                                                         \
   hipLaunchKernelGGL((xent32_fold_kernel<MAXC_, PREF_>), grid, dim3(256), lds, (hipStream_t)stream, logits_lo, labels, \
                      weights, nnz, dlogits_xfold, loss_partial, N, C, Hi, Wi, Ho, Wo, sy, sx)

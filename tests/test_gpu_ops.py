@@ -1510,7 +1510,8 @@ def test_fused_upsample_xent(L, void_w):
                                   (2, 32, 32, 512, 512, 21),    # the benchmark's row (MobileNetV2: logits at 1/16): two pixels per thread
                                   (1, 64, 64, 256, 256, 21),    # Xception-style 1/4 logits: three float4 per thread and source row
                                   (2, 16, 32, 64, 300, 8),      # second pixel of some threads only
-                                  (1, 8, 100, 16, 200, 32)])    # source rows too long for the prefetching form
+                                  (1, 8, 100, 16, 200, 32),     # source rows too long for the prefetching form
+                                  (1, 6, 8, 20, 24, 4)])        # prefetching form at an inexact vertical ratio (11 of 20 rows)
 def test_xent_fold_and_rows(L, dims, void_w, monkeypatch):
     """dl3_upsample_softmax_xent_fold + dl3_resize_bilinear_bwd_rows == the oracle's loss and the gradient it sends
     through the transposed legacy-bilinear resize, without the full-resolution dlogits"""

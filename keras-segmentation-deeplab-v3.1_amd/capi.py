@@ -149,6 +149,12 @@ def ptr(t, offset=0):
     return t.data_ptr() + 4 * offset
 
 
+def stream():
+    """the current torch stream's handle: the trailing `stream` argument of every launch"""
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
 def call(name, *args):
     """Call an int-returning op and raise on a non-zero status."""
     rc = getattr(lib(), name)(*args)

@@ -82,10 +82,7 @@ def dense_crf(images, masks, zero_unsure=True, return_q=False):
     if tuple(images.shape) != (B, H, W, 3):
         raise ValueError("images must be [B,H,W,3] matching the masks, got %r for masks %r" % (tuple(images.shape), mh.shape))
     dev = masks.device if on_device else torch.device("cuda", torch.cuda.current_device())
-    if torch.is_tensor(images):
-        im = images.to(dev).to(torch.uint8).contiguous()
-    else:
-        im = torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype("uint8"))).to(dev)
+    im = images_u8(images, dev)
     uniq = [np.unique(mh[b], return_inverse=True) for b in range(B)]
     L = max(len(c) for c, _ in uniq)
     if L > MAX_LABELS:

@@ -16,15 +16,73 @@ Reference call stack being replaced: Keras Model.predict / train_on_batch -> TF 
 import ctypes
 import math
 import os
+import types
 
 import numpy as np
 import torch
 
 from . import capi
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
+from .graph import raw_pixels
 
 _ACT = {"relu": ACT_RELU, "relu6": ACT_RELU6}
 V_SCALE, V_SHIFT, V_MEAN, V_INVSTD, V_CA, V_CB, V_CC, V_NEGMEAN = range(8)
+
+
+def pixels_to_device(x, device, non_blocking=False):
+    """raw 0-255 pixels (graph.raw_pixels) as a contiguous tensor on `device`: uint8 stays uint8 — decoded images cross
+    PCIe as bytes and are widened by the kernel that reads them —, every other dtype becomes float32"""
+    x = raw_pixels(x)
+    if torch.is_tensor(x):
+        t = x.to(device, non_blocking=non_blocking)
+        return (t if t.dtype == torch.uint8 else t.to(torch.float32)).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x)).to(device, non_blocking=non_blocking)
+
+
+def flat_f32(a, device, non_blocking=False):
+    """labels [B,HW,1] / sample weights [B,HW], a host array or a tensor, as a flat float32 tensor on `device`"""
+    if torch.is_tensor(a):
+        return a.reshape(-1).to(device, torch.float32, non_blocking=non_blocking)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))).to(device, non_blocking=non_blocking)
+
+
+def argmax_rows(t, M, C):
+    """dl3_argmax on the current stream: the first maximum of each row of the float32 device tensor t, read as [M,C]
+    -> int32 [M] on t's device"""
+    out = torch.empty(M, dtype=torch.int32, device=t.device)
+    capi.call("dl3_argmax", ptr(t), out.data_ptr(), M, C, capi.stream())
+    return out
+
+
+class Plan:
+    """One launch sequence of an engine under the capture rule all of its plans share: the first counted run() calls
+    `body` eagerly (module loading, allocator warm-up), the second captures it as one hipGraph and replays that, every
+    later one replays.  With eng.use_graph off nothing is counted or captured.  A capture that raises switches use_graph
+    off — for the whole engine: its other plans stop capturing too — and runs this call eagerly."""
+
+    def __init__(self, eng, body):
+        self.eng, self.body, self.calls, self.graph = eng, body, 0, None
+
+    def run(self):
+        if not self.eng.use_graph:
+            return self.body()
+        if self.calls >= 1 and self.graph is None:
+            torch.cuda.synchronize()
+            try:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):   # records the launches; nothing executes until the replay below
+                    self.body()
+                self.graph = g
+            except Exception as e:  # depends on the runtime
+                print("dl3: hipGraph capture failed (%s); running eagerly" % e)
+                self.eng.use_graph = False
+                torch.cuda.synchronize()
+                return self.body()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self.body()
+        self.calls += 1
 
 
 def _unbias_keras224(n, eps):
@@ -257,8 +315,8 @@ class Engine:
         self.bufs = []
         self.scratch_bytes = 0
         self.iteration = 0
-        self.graph = None
-        self._calls = 0
+        # the main plan: the whole step (fwd_bwd) of a training engine, the forward pass of an inference engine
+        self._main = Plan(self, self._run_main)
         self._keep = []
         self.drop_step = torch.zeros(1, dtype=torch.int64, device=self.device)  # device-side step number (dropout)
         self._plan_channels()
@@ -393,8 +451,6 @@ class Engine:
     def activate(self):
         """make this engine the one that layer.get_weights()/set_weights() talk to"""
         for l in self.model.layers:
-            if l._engine is not None and l._engine is not self:
-                pass
             l._engine = self
 
     # ------------------------------------------------------------------ op recording
@@ -1153,48 +1209,40 @@ class Engine:
     def set_input(self, x):
         """raw 0-255 pixels [B,H,W,3]: float32 (the reference's arrays), or uint8 (decoded images as they come from
         cv2.imread) — those cross PCIe as bytes and are widened on the device"""
-        if torch.is_tensor(x):
-            xt = x
-        elif isinstance(x, np.ndarray) and x.dtype == np.uint8:
-            xt = torch.from_numpy(np.ascontiguousarray(x))
-        else:
-            xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        self.xbuf.t.copy_(xt.reshape(-1).to(self.device, non_blocking=True))
+        self.xbuf.t.copy_(pixels_to_device(x, self.device, non_blocking=True).reshape(-1))
+
+    @property
+    def graph(self):
+        """the captured hipGraph of the main plan; None until its second call has captured it"""
+        return self._main.graph
+
+    def _run_main(self):
+        self.run_ops(self.ops_fwd)
+        if self.training:
+            self._run_bwd()
 
     def forward(self):
         """forward launch sequence; the inference engine replays it as one hipGraph from the second call on (68
-        launches of a few microseconds each: at batch 1 the Python/ctypes launch path costs more than the kernels)"""
+        launches of a few microseconds each: at batch 1 the Python/ctypes launch path costs more than the kernels).
+        A training engine's plan is the whole step (fwd_bwd): its forward() stays eager and does not count as a call"""
         self._prep()
-        if self.training or not self.use_graph:
+        if self.training:
             self.run_ops(self.ops_fwd)
-            return
-        if self._calls >= 1:
-            if self.graph is None:
-                torch.cuda.synchronize()
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self.run_ops(self.ops_fwd)
-                    self.graph = g
-                except Exception as e:  # pragma: no cover - depends on the runtime
-                    print("dl3: hipGraph capture failed (%s); running eagerly" % e)
-                    self.use_graph = False
-                    torch.cuda.synchronize()
-                    self.run_ops(self.ops_fwd)
-                    return
-            self.graph.replay()
         else:
-            self.run_ops(self.ops_fwd)
-        self._calls += 1
+            self._main.run()
+
+    def probs_device(self):
+        """forward() on the resident input, then the head's softmax: probabilities [B,H,W,C] on the device, a view of
+        self.probs (valid until the next call)"""
+        self.forward()
+        v = self.logits_view
+        capi.call("dl3_softmax_fwd", ptr(v.buf.t), ptr(self.probs), v.buf.M, v.C, capi.stream())
+        return self.probs.view(self.B, v.buf.H, v.buf.W, v.C)
 
     def predict(self, x):
         assert not self.training
         self.set_input(x)
-        self.forward()
-        v = self.logits_view
-        capi.call("dl3_softmax_fwd", ptr(v.buf.t), ptr(self.probs), v.buf.M, v.C,
-                  torch.cuda.current_stream().cuda_stream)
-        return self.probs.cpu().numpy().reshape(self.out_shape)
+        return self.probs_device().cpu().numpy().reshape(self.out_shape)
 
     def logits(self):
         v = self.logits_view
@@ -1207,9 +1255,7 @@ class Engine:
     def argmax(self, host=True):
         """int32 masks [B,H,W]: a numpy array, or with host=False the device tensor"""
         v = self.logits_view
-        out = torch.empty(v.buf.M, dtype=torch.int32, device=self.device)
-        capi.call("dl3_argmax", ptr(v.buf.t), out.data_ptr(), v.buf.M, v.C, torch.cuda.current_stream().cuda_stream)
-        out = out.reshape(self.B, v.buf.H, v.buf.W)
+        out = argmax_rows(v.buf.t, v.buf.M, v.C).reshape(self.B, v.buf.H, v.buf.W)
         return out.cpu().numpy() if host else out
 
     def set_targets(self, y, sw=None, fill_weights=True):
@@ -1219,22 +1265,15 @@ class Engine:
         M = self.logits_view.buf.M
         if not self.training:
             self._eval_setup()
-        if torch.is_tensor(y):
-            yt = y.reshape(-1).to(torch.float32)
-        else:
-            yt = torch.from_numpy(np.ascontiguousarray(np.asarray(y, np.float32).reshape(-1)))
+        yt = flat_f32(y, self.device, non_blocking=True)
         assert yt.numel() == M, (yt.numel(), M)
-        self.labels.copy_(yt.to(self.device, non_blocking=True))
-        if sw is None and not fill_weights:
-            pass
-        elif sw is None:
+        self.labels.copy_(yt)
+        if sw is not None:
+            self.sweights.copy_(flat_f32(sw, self.device, non_blocking=True))
+        elif fill_weights:
             # Keras without sample weights: plain mean over all B*HW pixels; void rows contribute zero loss and zero
             # gradient through the one-hot (utils.py:129), not through a weight
-            capi.call("dl3_fill", ptr(self.sweights), 1.0, M, torch.cuda.current_stream().cuda_stream)
-        elif torch.is_tensor(sw):
-            self.sweights.copy_(sw.reshape(-1).to(self.device, torch.float32, non_blocking=True))
-        else:
-            self.sweights.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(sw, np.float32).reshape(-1))).to(self.device))
+            capi.call("dl3_fill", ptr(self.sweights), 1.0, M, capi.stream())
 
     def count_nnz(self):
         """count(w != 0) of the resident sample weights (device count, one scalar read back)"""
@@ -1270,16 +1309,12 @@ class Engine:
         """after forward(): per-image, per-class pixel counts [B,3,C] of the argmax mask against labels y
         (dl3_argmax + dl3_seg_counts on the device; utils.Jaccard_from_counts turns them into the metric)"""
         v = self.logits_view
-        st = torch.cuda.current_stream().cuda_stream
-        pred = torch.empty(v.buf.M, dtype=torch.int32, device=self.device)
-        capi.call("dl3_argmax", ptr(v.buf.t), pred.data_ptr(), v.buf.M, v.C, st)
-        if torch.is_tensor(y):
-            yt = y.reshape(-1).to(self.device, torch.float32)
-        else:
-            yt = torch.from_numpy(np.ascontiguousarray(np.asarray(y, np.float32).reshape(-1))).to(self.device)
+        pred = argmax_rows(v.buf.t, v.buf.M, v.C)
+        yt = flat_f32(y, self.device)
         assert yt.numel() == v.buf.M, (yt.numel(), v.buf.M)
         counts = torch.empty(self.B, 3, v.C, dtype=torch.int32, device=self.device)
-        capi.call("dl3_seg_counts", pred.data_ptr(), yt.data_ptr(), self.B, v.buf.M // self.B, v.C, counts.data_ptr(), st)
+        capi.call("dl3_seg_counts", pred.data_ptr(), yt.data_ptr(), self.B, v.buf.M // self.B, v.C, counts.data_ptr(),
+                  capi.stream())
         return counts.cpu().numpy()
 
     # ------------------------------------------------------------------ evaluation plan (DESIGN.md §10)
@@ -1294,33 +1329,36 @@ class Engine:
             return ev
         if self.training:
             raise RuntimeError("Engine.evaluate_batch needs an inference engine (training=False)")
-        v = self.logits_view
-        M, C, B, lib = v.buf.M, v.C, self.B, self.lib
-        ops = list(self.ops_fwd)
-        form, src, dims = self._tail_source()
-        if form != "plain":
-            # the fused kernel's own limits (C <= 32, LDS staging): its *_partials query answers 0 for a shape it refuses
-            P = getattr(lib, "dl3_eval_tail_%s_partials" % form)(*dims)
-            if P <= 0:
-                form = "plain"
-        if form == "plain":
-            P = lib.dl3_eval_tail_plain_partials(B, M // B, C)
-            if P <= 0:
-                raise capi.DL3Error("dl3_eval_tail_plain does not support %d classes" % C)
-            src, dims = ptr(v.buf.t), (B, M // B, C)
-        else:
-            ops.pop()
+        M, C, B = self.logits_view.buf.M, self.logits_view.C, self.B
+
+        def partials(form, dims):
+            return getattr(self.lib, "dl3_eval_tail_%s_partials" % form)(*dims)
+        # the fused kernel's own limits (C <= 32, LDS staging): its *_partials query answers 0 for a shape it refuses
+        form, src, dims, ops = self._fused_head(partials)
+        P = partials(form, dims)
+        if P <= 0:
+            raise capi.DL3Error("dl3_eval_tail_plain does not support %d classes" % C)
         # labels / weights of the batch (set_targets), the tail's own buffers and ONE record of its results:
         # loss_sum double[B] | nnz int32[B] | counts int32[B][3][C]
         self.labels = self.zeros(M)
         self.sweights = self.zeros(M)
         rec_bytes = (8 * B + 4 * B + 4 * B * 3 * C + 15) // 16 * 16
-        ev = dict(form=form, src=src, dims=dims, ops=ops, plans={}, n=0, rec_bytes=rec_bytes,
-                  part=self.empty(2 * B * P), mask=torch.empty(M, dtype=torch.int32, device=self.device),
-                  rec=torch.zeros(rec_bytes, dtype=torch.uint8, device=self.device),
-                  results=torch.zeros(8, rec_bytes, dtype=torch.uint8, device=self.device))
-        self._eval = ev
+        self._eval = ev = types.SimpleNamespace(
+            form=form, src=src, dims=dims, ops=ops, plans={}, n=0, rec_bytes=rec_bytes, part=self.empty(2 * B * P),
+            mask=torch.empty(M, dtype=torch.int32, device=self.device),
+            rec=torch.zeros(rec_bytes, dtype=torch.uint8, device=self.device),
+            results=torch.zeros(8, rec_bytes, dtype=torch.uint8, device=self.device))
         return ev
+
+    def _fused_head(self, accepts=None):
+        """what the evaluation plan and the CRF-unary plan share: (form, source pointer, dims) of _tail_source() and the
+        forward op list, without its last launch where a fused form reads in front of that launch.  accepts(form, dims):
+        the fused kernel's own shape query; an answer <= 0 falls back to the plain form, and nothing is dropped."""
+        form, src, dims = self._tail_source()
+        if form != "plain" and accepts is not None and accepts(form, dims) <= 0:
+            v = self.logits_view
+            form, src, dims = "plain", ptr(v.buf.t), (self.B, v.buf.M // self.B, v.C)
+        return form, src, dims, (self.ops_fwd[:-1] if form != "plain" else list(self.ops_fwd))
 
     def _tail_source(self):
         """what a fused tail (evaluation, CRF unary) may read instead of the full-resolution logits: ("bilinear", pointer,
@@ -1343,26 +1381,26 @@ class Engine:
 
     def eval_op_names(self, confusion=None, mask=False):
         """the launch names of the evaluation plan (tests: no final resize / phase shift / softmax in it)"""
-        return [rec[0] for rec in self._eval_plan(confusion, True, mask)["ops"]]
+        return [rec[0] for rec in self._eval_plan(confusion, True, mask)[1]]
 
     def _eval_plan(self, confusion, weighted, mask):
+        """(Plan, launch list) of one (confusion pointer, weighted, mask) variant"""
         ev = self._eval_setup()
         key = (0 if confusion is None else confusion.data_ptr(), bool(weighted), bool(mask))
-        plan = ev["plans"].get(key)
-        if plan is None:
+        if key not in ev.plans:
             B, C = self.B, self.logits_view.C
             if confusion is not None and (confusion.dtype != torch.int64 or confusion.numel() != C * C
                                           or not confusion.is_contiguous() or confusion.device != self.device):
                 raise ValueError("confusion must be a contiguous int64 [%d,%d] tensor on %s" % (C, C, self.device))
-            base = ev["rec"].data_ptr()
-            args = [ev["src"], ptr(self.labels), ptr(self.sweights) if weighted else None, ptr(ev["part"]), base,
+            base = ev.rec.data_ptr()
+            args = [ev.src, ptr(self.labels), ptr(self.sweights) if weighted else None, ptr(ev.part), base,
                     base + 8 * B, base + 12 * B, None if confusion is None else confusion.data_ptr(),
-                    ev["mask"].data_ptr() if mask else None] + list(ev["dims"])
-            name = "dl3_eval_tail_" + ev["form"]
-            plan = dict(ops=ev["ops"] + [(name, getattr(self.lib, name), args, None)], calls=0, graph=None,
-                        confusion=confusion)
-            ev["plans"][key] = plan
-        return plan
+                    ev.mask.data_ptr() if mask else None] + list(ev.dims)
+            name = "dl3_eval_tail_" + ev.form
+            ops = ev.ops + [(name, getattr(self.lib, name), args, None)]
+            # (confusion rides along so that the tensor behind the captured pointer stays alive)
+            ev.plans[key] = (Plan(self, lambda: self.run_ops(ops)), ops, confusion)
+        return ev.plans[key][:2]
 
     def evaluate_batch(self, x, y, sw=None, confusion=None, mask=False):
         """forward + evaluation tail on (x, y, sw), everything on the device: the batch's loss sums, count(w != 0) and
@@ -1372,50 +1410,36 @@ class Engine:
         is replayed as a hipGraph of its own from its second call on.
         The host waits for the stream to drain before it enqueues (the trap recorded in train_step: a graph replay
         behind a pageable device-to-host copy)."""
-        plan = self._eval_plan(confusion, sw is not None, mask)
+        plan, _ = self._eval_plan(confusion, sw is not None, mask)
         ev = self._eval
         torch.cuda.current_stream().synchronize()
         self.set_input(x)
         self.set_targets(y, sw, fill_weights=False)
         self._prep()
-        if self.use_graph and plan["calls"] >= 1:
-            if plan["graph"] is None:
-                torch.cuda.synchronize()
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self.run_ops(plan["ops"])
-                    plan["graph"] = g
-                except Exception as e:  # pragma: no cover - depends on the runtime
-                    print("dl3: hipGraph capture failed (%s); running eagerly" % e)
-                    self.use_graph = False
-                    torch.cuda.synchronize()
-            if plan["graph"] is not None:
-                plan["graph"].replay()
-            else:
-                self.run_ops(plan["ops"])
-        else:
-            self.run_ops(plan["ops"])
-        plan["calls"] += 1
-        if ev["n"] == ev["results"].shape[0]:
-            grown = torch.zeros(2 * ev["n"], ev["rec_bytes"], dtype=torch.uint8, device=self.device)
-            grown[:ev["n"]].copy_(ev["results"])
-            ev["results"] = grown
-        ev["results"][ev["n"]].copy_(ev["rec"])
-        ev["n"] += 1
+        plan.run()
+        if ev.n == ev.results.shape[0]:
+            grown = torch.zeros(2 * ev.n, ev.rec_bytes, dtype=torch.uint8, device=self.device)
+            grown[:ev.n].copy_(ev.results)
+            ev.results = grown
+        ev.results[ev.n].copy_(ev.rec)
+        ev.n += 1
         if mask:
             v = self.logits_view
-            return ev["mask"].reshape(self.B, v.buf.H, v.buf.W)
+            return ev.mask.reshape(self.B, v.buf.H, v.buf.W)
         return None
+
+    def discard_evaluation(self):
+        """forget the records written since the last read_evaluation() (a pass that starts over)"""
+        self._eval_setup().n = 0
 
     def read_evaluation(self):
         """the records written since the last read, in ONE device-to-host copy behind a host-side stream synchronisation:
         (loss_sum [n,B] float64, nnz [n,B] int32, counts [n,B,3,C] int32); the record counter starts over"""
         ev = self._eval_setup()
-        n, B, C = ev["n"], self.B, self.logits_view.C
+        n, B, C = ev.n, self.B, self.logits_view.C
         torch.cuda.current_stream().synchronize()
-        raw = ev["results"][:n].cpu().numpy() if n else np.zeros((0, ev["rec_bytes"]), np.uint8)
-        ev["n"] = 0
+        raw = ev.results[:n].cpu().numpy() if n else np.zeros((0, ev.rec_bytes), np.uint8)
+        ev.n = 0
         loss = np.ascontiguousarray(raw[:, :8 * B]).view(np.float64).reshape(n, B)
         nnz = np.ascontiguousarray(raw[:, 8 * B:12 * B]).view(np.int32).reshape(n, B)
         counts = np.ascontiguousarray(raw[:, 12 * B:12 * B + 12 * B * C]).view(np.int32).reshape(n, B, 3, C)
@@ -1426,28 +1450,19 @@ class Engine:
         """the plan behind crf_unary: like the evaluation plan, the forward op list minus the final resize / phase-shift
         launch where that launch only spreads materialised low-resolution logits (`ops_fwd` itself stays as it is), ending
         in dl3_crf_unary_bilinear / _shuffle on those; any other graph keeps its whole forward plan and ends in
-        dl3_crf_unary_plain on the head's logits.  No softmax launch either way."""
-        cp = getattr(self, "_crf", None)
-        if cp is not None:
-            return cp
-        if self.training:
-            raise RuntimeError("Engine.crf_unary needs an inference engine (training=False)")
-        ops = list(self.ops_fwd)
-        form, src, dims = self._tail_source()
-        if form != "plain":
-            ops.pop()
-        self._crf = dict(form=form, src=src, dims=dims, ops=ops)
+        dl3_crf_unary_plain on the head's logits.  No softmax launch either way.  -> (form, source, dims, forward ops)"""
+        if getattr(self, "_crf", None) is None:
+            if self.training:
+                raise RuntimeError("Engine.crf_unary needs an inference engine (training=False)")
+            self._crf = self._fused_head()
         return self._crf
 
     def _crf_ops(self, U_ptr, scale, clip):
-        cp = self._crf_setup()
+        form, src, dims, ops = self._crf_setup()
         sc, cl = (0.0 if scale is None else float(scale)), (0.0 if clip is None else float(clip))
-        name = "dl3_crf_unary_" + cp["form"]
-        if cp["form"] == "plain":
-            args = [cp["src"], 0, U_ptr] + list(cp["dims"]) + [sc, cl]
-        else:
-            args = [cp["src"], U_ptr] + list(cp["dims"]) + [sc, cl]
-        return cp["ops"] + [(name, getattr(self.lib, name), args, None)]
+        name = "dl3_crf_unary_" + form
+        args = ([src, 0, U_ptr] if form == "plain" else [src, U_ptr]) + list(dims) + [sc, cl]
+        return ops + [(name, getattr(self.lib, name), args, None)]
 
     def crf_unary_op_names(self):
         """the launch names of the CRF unary plan (tests: which form, and no final resize / phase shift / softmax)"""
@@ -1484,28 +1499,9 @@ class Engine:
         return MAP.reshape(self.B, v.buf.H, v.buf.W)
 
     def fwd_bwd(self):
-        """forward + loss + backward on the resident batch (the benchmarked hot path)"""
+        """forward + loss + backward on the resident batch (the benchmarked hot path): the main plan"""
         self._prep()
-        if self.use_graph and self._calls >= 1:
-            if self.graph is None:
-                # the first call ran eagerly (module loading, allocator warm-up); capture one replayable hipGraph now
-                torch.cuda.synchronize()
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self.run_ops(self.ops_fwd)
-                        self._run_bwd()
-                    self.graph = g
-                except Exception as e:  # pragma: no cover - depends on the runtime
-                    print("dl3: hipGraph capture failed (%s); running eagerly" % e)
-                    self.use_graph = False
-                    torch.cuda.synchronize()
-                    return self.fwd_bwd()
-            self.graph.replay()
-        else:
-            self.run_ops(self.ops_fwd)
-            self._run_bwd()
-        self._calls += 1
+        self._main.run()
 
     def _run_bwd(self):
         if self.fork and self._side:

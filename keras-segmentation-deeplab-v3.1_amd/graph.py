@@ -17,6 +17,20 @@ _uids = collections.defaultdict(int)
 _rng = np.random.default_rng(0)
 
 
+def raw_pixels(x):
+    """raw 0-255 pixels as the package takes them: a device tensor or a uint8 array (decoded images) as it is, anything
+    else as a float32 array (the reference's arrays)"""
+    if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
+        x = np.asarray(x, np.float32)
+    return x
+
+
+def batches(n, batch_size):
+    """the slices that cut n samples into forward batches: min(batch_size, n) consecutive samples, a short last one"""
+    bs = min(int(batch_size), n)
+    return [slice(i, i + bs) for i in range(0, n, bs)]
+
+
 def clear_session(seed=0):
     """keras.backend.clear_session(): reset auto-naming counters (and the weight-init RNG)."""
     global _rng
@@ -569,15 +583,11 @@ class Model:
         return eng
 
     def predict(self, x, batch_size=32, verbose=0):
-        if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
-            x = np.asarray(x, np.float32)
-        n = x.shape[0]
-        bs = min(int(batch_size), n)
+        x = raw_pixels(x)
         outs = []
-        for i in range(0, n, bs):
-            xb = x[i:i + bs]
-            eng = self._engine(xb.shape[0], False)
-            outs.append(eng.predict(xb))
+        for s in batches(x.shape[0], batch_size):
+            xb = x[s]
+            outs.append(self._engine(xb.shape[0], False).predict(xb))
         return np.concatenate(outs, axis=0)
 
     def predict_mask(self, x, batch_size=32, crf=False, crf_unary="labels"):
@@ -594,13 +604,10 @@ class Model:
         masks are copied out."""
         if crf and crf_unary not in ("labels", "softmax"):
             raise ValueError("predict_mask: crf_unary must be 'labels' or 'softmax', got %r" % (crf_unary,))
-        if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
-            x = np.asarray(x, np.float32)
-        n = x.shape[0]
-        bs = min(int(batch_size), n)
+        x = raw_pixels(x)
         outs = []
-        for i in range(0, n, bs):
-            xb = x[i:i + bs]
+        for s in batches(x.shape[0], batch_size):
+            xb = x[s]
             eng = self._engine(xb.shape[0], False)
             eng.set_input(xb)
             if crf and crf_unary == "softmax":
@@ -670,14 +677,10 @@ class Model:
         if device:
             return self._evaluate_device(self._xy_batches(x, y, sample_weight, batch_size))[0]
         from . import utils as U
-        if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
-            x = np.asarray(x, np.float32)
-        y = np.asarray(y)
-        n = x.shape[0]
-        bs = min(int(batch_size), n)
+        x, y = raw_pixels(x), np.asarray(y)
         counts, num, den = [], 0.0, 0.0
-        for i in range(0, n, bs):
-            xb, yb = x[i:i + bs], y[i:i + bs]
+        for s in batches(x.shape[0], batch_size):
+            xb, yb = x[s], y[s]
             eng = self._engine(xb.shape[0], False)
             probs = eng.predict(xb)
             counts.append(eng.seg_counts(yb))
@@ -687,7 +690,7 @@ class Model:
             # no sample weights: Keras takes the plain mean over all B*HW pixels (void rows contribute 0 through the
             # one-hot, utils.py:129); with weights: sum(l*w) / count(w != 0)
             w = np.ones(yb.shape[:2], np.float64) if sample_weight is None else \
-                np.asarray(sample_weight[i:i + bs], np.float64).reshape(xb.shape[0], -1)
+                np.asarray(sample_weight[s], np.float64).reshape(xb.shape[0], -1)
             ell = U.sparse_crossentropy_ignoring_last_label(yb, probs)
             num += float((ell * w).sum() / max((w != 0).mean(), 1e-30) / w.size) * xb.shape[0]
             den += xb.shape[0]
@@ -697,12 +700,9 @@ class Model:
     # -- evaluation on the device ------------------------------------------------------------------
     @staticmethod
     def _xy_batches(x, y, sample_weight, batch_size):
-        if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
-            x = np.asarray(x, np.float32)
-        n = x.shape[0]
-        bs = min(int(batch_size), n)
-        for i in range(0, n, bs):
-            yield x[i:i + bs], y[i:i + bs], (None if sample_weight is None else sample_weight[i:i + bs])
+        x = raw_pixels(x)
+        for s in batches(x.shape[0], batch_size):
+            yield x[s], y[s], (None if sample_weight is None else sample_weight[s])
 
     @staticmethod
     def _generator_batches(generator, steps=None):
@@ -725,7 +725,7 @@ class Model:
             eng = self._engine(xb.shape[0], False)
             if id(eng) not in fresh:
                 fresh.add(id(eng))
-                eng._eval_setup()["n"] = 0
+                eng.discard_evaluation()
             eng.evaluate_batch(xb, yb, swb, confusion=confusion)
             used.append(eng)
         if not used:

@@ -113,11 +113,6 @@ def check_args(model, x, stride, blend, batch_size, output):
 
 
 # ---------------------------------------------------------------------------------------------- launch wrappers
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 def gather(img, window, stride, k0, nw, dst, pad_value=127.5):
     """dl3_slide_gather on the current stream: img [Hi,Wi,3] uint8 / float32 cuda tensor -> dst, nw * H * W * 3 floats"""
     import torch
@@ -125,7 +120,7 @@ def gather(img, window, stride, k0, nw, dst, pad_value=127.5):
     assert img.is_contiguous() and dst.is_contiguous() and dst.dtype == torch.float32
     assert img.dtype in (torch.uint8, torch.float32) and dst.numel() == nw * window[0] * window[1] * 3
     capi.call("dl3_slide_gather", img.data_ptr(), U8 if img.dtype == torch.uint8 else F32, Hi, Wi, window[0], window[1],
-              stride[0], stride[1], int(k0), int(nw), float(pad_value), dst.data_ptr(), _stream())
+              stride[0], stride[1], int(k0), int(nw), float(pad_value), dst.data_ptr(), capi.stream())
     return dst
 
 
@@ -135,7 +130,7 @@ def accumulate(probs, acc, window, stride, k0, blend):
     Hi, Wi, _ = acc.shape
     assert probs.is_contiguous() and acc.is_contiguous() and (H, W) == tuple(window) and acc.shape[2] == C
     capi.call("dl3_slide_accumulate", probs.data_ptr(), acc.data_ptr(), None, Hi, Wi, H, W, C, stride[0], stride[1], int(k0),
-              int(nw), BLENDS[blend], _stream())
+              int(nw), BLENDS[blend], capi.stream())
     return acc
 
 
@@ -146,7 +141,7 @@ def finalize(acc, window, stride, blend, output):
     mask = torch.empty(Hi, Wi, dtype=torch.int32, device=acc.device) if output == "mask" else None
     capi.call("dl3_slide_finalize", acc.data_ptr(), None, None if output == "mask" else acc.data_ptr(),
               None if mask is None else mask.data_ptr(), Hi, Wi, window[0], window[1], C, stride[0], stride[1], BLENDS[blend],
-              _stream())
+              capi.stream())
     return acc if mask is None else mask
 
 
@@ -177,17 +172,11 @@ def _runs(chunk):
     return runs
 
 
-def _device_image(im, device):
-    import torch
-    t = im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))
-    return t.to(device).contiguous()
-
-
 def predict_sliding(model, x, stride=None, blend="uniform", batch_size=8, output="mask", pad_value=127.5):
     """Model.predict_sliding (graph.py)"""
     images, stacked, stride = check_args(model, x, stride, blend, batch_size, output)
     import torch
-    from .tta import _forward_probs
+    from .engine import pixels_to_device
     H, W = model.input.shape[:2]
     window = (H, W)
     sizes = [tuple(int(s) for s in im.shape[:2]) for im in images]
@@ -207,10 +196,10 @@ def predict_sliding(model, x, stride=None, blend="uniform", batch_size=8, output
         xb = eng.xbuf.t
         for i, k0, nw, off in runs:
             if i not in live:
-                live[i] = (_device_image(images[i], eng.device),
+                live[i] = (pixels_to_device(images[i], eng.device),
                            torch.zeros(sizes[i] + (v.C,), dtype=torch.float32, device=eng.device))
             gather(live[i][0], window, stride, k0, nw, xb[off * H * W * 3:(off + nw) * H * W * 3], pad_value)
-        probs = _forward_probs(eng)
+        probs = eng.probs_device()
         for i, k0, nw, off in runs:
             accumulate(probs[off:off + nw], live[i][1], window, stride, k0, blend)
             if k0 + nw - 1 == last_k[i]:

@@ -68,11 +68,6 @@ def check_args(model, scales, output, crf, factory):
 
 
 # ---------------------------------------------------------------------------------------------- launch wrappers
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 def resize_image(src, dst, flip=False):
     """dl3_tta_resize_image on the current stream: src [B,Hi,Wi,3] uint8 or float32 cuda tensor -> dst float32 cuda
     tensor of B*Ho*Wo*3 elements shaped [B,Ho,Wo,3]"""
@@ -82,7 +77,7 @@ def resize_image(src, dst, flip=False):
     assert src.is_contiguous() and dst.is_contiguous() and dst.dtype == torch.float32
     assert src.dtype in (torch.uint8, torch.float32) and src.shape[3] == 3 and dst.shape[3] == 3 and dst.shape[0] == B
     capi.call("dl3_tta_resize_image", src.data_ptr(), U8 if src.dtype == torch.uint8 else F32, dst.data_ptr(), B, Hi, Wi,
-              Ho, Wo, int(bool(flip)), _stream())
+              Ho, Wo, int(bool(flip)), capi.stream())
     return dst
 
 
@@ -94,7 +89,7 @@ def accumulate(probs, acc, flip=False, first=False, n_passes_if_last=0):
     assert probs.is_contiguous() and acc.is_contiguous() and probs.dtype == acc.dtype == torch.float32
     assert acc.shape[0] == B and acc.shape[3] == C
     capi.call("dl3_tta_accumulate", probs.data_ptr(), acc.data_ptr(), B, Hi, Wi, Ho, Wo, C, int(bool(flip)),
-              int(bool(first)), int(n_passes_if_last), _stream())
+              int(bool(first)), int(n_passes_if_last), capi.stream())
     return acc
 
 
@@ -151,35 +146,14 @@ def hand_over(src, dst):
     dst.dirty = True
 
 
-def _device_batch(xb, device):
-    """[b,H,W,3] raw pixels as a contiguous uint8 or float32 tensor on the device"""
-    import torch
-    if torch.is_tensor(xb):
-        t = xb.to(device)
-        if t.dtype != torch.uint8:
-            t = t.to(torch.float32)
-        return t.contiguous()
-    if isinstance(xb, np.ndarray) and xb.dtype == np.uint8:
-        return torch.from_numpy(np.ascontiguousarray(xb)).to(device)
-    return torch.from_numpy(np.ascontiguousarray(xb, dtype=np.float32)).to(device)
-
-
-def _forward_probs(eng):
-    """the engine's forward plan on its resident input, then its softmax: probabilities [B,H,W,C] on the device"""
-    from .capi import ptr
-    eng.forward()
-    v = eng.logits_view
-    capi.call("dl3_softmax_fwd", ptr(v.buf.t), ptr(eng.probs), v.buf.M, v.C, _stream())
-    return eng.probs.view(eng.B, v.buf.H, v.buf.W, v.C)
-
-
 def averaged_probs(model, xb, passes, factory=None):
     """one batch through every pass: the averaged probabilities, a float32 cuda tensor [b,H,W,C] (a fresh tensor)"""
     import torch
+    from .engine import pixels_to_device
     b = int(xb.shape[0])
     H, W = model.input.shape[:2]
     main = model._engine(b, False)   # brings the model's current weights to this engine's arenas
-    xd = _device_batch(xb, main.device)
+    xd = pixels_to_device(xb, main.device)
     if tuple(xd.shape) != (b, H, W, 3):
         raise ValueError("predict_multiscale: x must be [B,%d,%d,3], got %r" % (H, W, tuple(xd.shape)))
     acc, fresh = None, set()
@@ -192,7 +166,7 @@ def averaged_probs(model, xb, passes, factory=None):
                 hand_over(main, eng)
                 fresh.add(id(eng))
         resize_image(xd, eng.xbuf.t.view(b, hs, ws, 3), flipped)
-        probs = _forward_probs(eng)
+        probs = eng.probs_device()
         if acc is None:
             acc = torch.empty(b, H, W, probs.shape[3], dtype=torch.float32, device=main.device)
         accumulate(probs, acc, flipped, first=(i == 0), n_passes_if_last=len(passes) if i == len(passes) - 1 else 0)
@@ -205,30 +179,26 @@ def predict_multiscale(model, x, scales=DEFAULT_SCALES, flip=True, batch_size=8,
     if not flip:
         passes = [p for p in passes if not p[3]]
     import torch
-    if not hasattr(x, "data_ptr") and not (isinstance(x, np.ndarray) and x.dtype == np.uint8):
-        x = np.asarray(x, np.float32)
+    from .engine import argmax_rows, pixels_to_device
+    x = G.raw_pixels(x)
     H, W = model.input.shape[:2]
     if int(batch_size) <= 0:
         raise ValueError("predict_multiscale: batch_size must be positive, got %r" % (batch_size,))
     if len(x.shape) != 4 or tuple(x.shape[1:]) != (H, W, 3) or x.shape[0] == 0:
         raise ValueError("predict_multiscale: x must be [B,%d,%d,3] with B >= 1, got %r" % (H, W, tuple(x.shape)))
-    n = x.shape[0]
-    bs = min(int(batch_size), n)
     outs = []
-    for i in range(0, n, bs):
-        xb = x[i:i + bs]
+    for s in G.batches(x.shape[0], batch_size):
+        xb = x[s]
         acc = averaged_probs(model, xb, passes, factory)
         b, C = acc.shape[0], acc.shape[3]
         if output == "probs":
             outs.append(acc.cpu().numpy().reshape((b,) + tuple(model.output.shape)))
         elif crf:
             from .crf import dense_crf_softmax
-            outs.append(dense_crf_softmax(xb if torch.is_tensor(xb) else _device_batch(xb, acc.device), probs=acc)
+            outs.append(dense_crf_softmax(xb if torch.is_tensor(xb) else pixels_to_device(xb, acc.device), probs=acc)
                         .to(torch.int32).cpu().numpy())
         else:
-            mask = torch.empty(b * H * W, dtype=torch.int32, device=acc.device)
-            capi.call("dl3_argmax", acc.data_ptr(), mask.data_ptr(), b * H * W, C, _stream())
-            outs.append(mask.reshape(b, H, W).cpu().numpy())
+            outs.append(argmax_rows(acc, b * H * W, C).reshape(b, H, W).cpu().numpy())
     return np.concatenate(outs, axis=0)
 
 

@@ -232,6 +232,40 @@ def test_graph_replay_and_determinism():
     assert not torch.equal(seq[True][1], seq[True][2])  # a new mask every step
 
 
+def test_main_plan_capture_rule():
+    """engine.Plan on the device.  Inference engine: forward() runs eagerly, captures on its second call and replays on its
+    third, and every call's logits are those of a use_graph=False engine, bit for bit.  Training engine: forward() is
+    eager and does not advance the step plan — the fwd_bwd() behind two forward() calls is still the eager one, the next
+    captures —, and the replayed step's gradients and loss are the eager step's, bit for bit."""
+    from tests.test_gpu_eval import _data, _model
+    model = _model("mobilenetv2", "original")
+    x, y, sw = _data(2, 3)
+    eager = model._engine(2, False, use_graph=False)
+    eager.set_input(x)
+    eager.forward()
+    want = eager.logits()
+    assert eager.graph is None
+    eng = model._engine(2, False, use_graph=True)
+    eng.set_input(x)
+    for call in range(3):
+        eng.forward()
+        assert (eng.graph is not None) == (call >= 1), call
+        assert np.array_equal(eng.logits(), want), call
+    tr = model._engine(2, True, dropout=False, use_graph=True)
+    tr.set_input(x)
+    tr.set_targets(y, sw)
+    tr.forward()
+    tr.forward()
+    assert tr.graph is None
+    tr.fwd_bwd()   # the step's first call: eager
+    assert tr.graph is None
+    g0, l0 = tr.grads.clone(), float(tr.loss[0].item())
+    tr.fwd_bwd()   # captured + replayed
+    assert tr.graph is not None
+    assert torch.equal(tr.grads, g0) and float(tr.loss[0].item()) == l0
+    assert np.isfinite(l0) and float(g0.abs().max()) > 0
+
+
 def test_dropout_mask_changes_every_step():
     """Dropout(0.1) (deeplabv3p.py:410) must draw a new keep mask every training step — also when the step is a replayed
     hipGraph, whose launch arguments are frozen (the step number lives in device memory) — and a different one on every

@@ -98,7 +98,7 @@ def predict(a):
     total = 0.0
     for s, hs, ws, flipped in tta.pass_list((S, S), tta.DEFAULT_SCALES, False):
         eng = (model if (hs, ws) == (S, S) else tta.sibling(model, hs, ws))._engine(B, False)
-        ms, lo, hi = _median_ms(lambda eng=eng: tta._forward_probs(eng), a.reps, 2)
+        ms, lo, hi = _median_ms(lambda eng=eng: eng.probs_device(), a.reps, 2)
         total += 2 * ms
         print("  forward + softmax at %4d x %-4d %8.3f ms (%.3f - %.3f), twice" % (hs, ws, ms, lo, hi))
     print("  sum of the twelve forward passes %.2f ms; the call's remainder %.2f ms (resize, accumulate, argmax, weight "

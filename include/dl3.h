@@ -486,6 +486,39 @@ size_t dl3_augment_workspace_bytes(int B, int H, int W, int flags);
 int dl3_augment(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H, int W, int flags,
                 const int *img_params, const int *lut, const int *warp_tab, const int *clahe_i, const float *clahe_f,
                 int C, float *X, void *labels_out, void *workspace, size_t workspace_bytes, void *stream);
+/* dl3_augment with the label sets handed in: present[B][8], bit v of image b set when label value v occurs in its map
+ * BEFORE any resize (dl3_cv_resize writes them from the source-size maps; the reference takes np.unique(label) there,
+ * utils.py:317).  dl3_augment derives the same sets from its own `labels`.  Everything else is dl3_augment's contract. */
+int dl3_augment_present(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H, int W,
+                        int flags, const int *img_params, const int *lut, const int *warp_tab, const int *clahe_i,
+                        const float *clahe_f, int C, const int *present, float *X, void *labels_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* ---- cv2.resize in front of the augmentation (utils.py:322-324, :421-422): a ragged batch -> the uniform one -------------
+ * B decoded images of DIFFERENT sizes lie back to back in image_pool (uint8, BGR, [Hs][Ws][3] each), their label maps in
+ * label_pool (label_dtype, [Hs][Ws] each).  Per image, in the reference's order: [blur 5x5 at the source size, reflect-101
+ * at the image's own borders] -> mode 0: cv2.resize to H x W (INTER_LINEAR for the image: 11-bit coefficients and cv2's
+ * two-pass integer rounding; INTER_NEAREST for the label map) | mode 1: the H x W crop at (crop_x, crop_y).  Outputs:
+ *   images_out[B][H][W][3] uint8, labels_out[B][H][W] (label_dtype): the input of dl3_augment / dl3_augment_present
+ *   present[B][8] (nullable): the 256-bit set of label values of each SOURCE-size map (int32 values outside 0..255 set
+ *                 nothing); zeroed here
+ * Either pool may be NULL together with its output (images only, or maps only).  Tables, int32, in device memory:
+ *   desc[B][12] = {image offset (bytes into image_pool), label offset (elements into label_pool), Hs, Ws, blur_on, mode,
+ *                  crop_x, crop_y, table offset (ints into tab), 0, 0, 0}
+ *   tab: per distinct source size 4W + 4H ints: xs[W], xa0[W], xa1[W], xn[W], ys[H], yb0[H], yb1[H], yn[H] — the first
+ *        source column (clamped to 0..Ws-1) and its two coefficients (sum 2048), the nearest column; the first source row
+ *        as floor() left it (the device clamps both taps) and its coefficients, the nearest row.  Mode-1 images read none.
+ * The host takes every floating-point decision (augment.resize_tables); the device does integer arithmetic only.
+ * THE DEVICE TRUSTS desc AND tab: the caller (augment.front_tables) checks that every image and map lies inside its pool,
+ * every crop inside its image and every table index inside its source before the upload.  max_hs / max_ws: the largest
+ * Hs / Ws of the batch (they size the grids of the blur and the label-set pass).  blur_any: some desc has blur_on — the
+ * blurred copies go to `workspace` (dl3_cv_resize_workspace_bytes(image_pool_bytes, 1); nothing is needed without blur).
+ * One launch per stage for the whole batch.  -1 for sizes below 1, a missing output or a short workspace; -4 for a label
+ * dtype other than DL3_LABEL_U8 / DL3_LABEL_I32.  Integer atomics only. */
+size_t dl3_cv_resize_workspace_bytes(size_t image_pool_bytes, int blur_any);
+int dl3_cv_resize(const unsigned char *image_pool, size_t image_pool_bytes, const void *label_pool, int label_dtype, int B,
+                  int max_hs, int max_ws, int H, int W, int blur_any, const int *desc, const int *tab, void *images_out,
+                  void *labels_out, int *present, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- dense-CRF post-processing (do_crf, utils.py:74-91): exact mean-field inference, DESIGN.md §9 -----------------------
  * The model the reference configures in pydensecrf — unary from labels, a Gaussian position kernel and a bilateral

@@ -11,6 +11,7 @@
 //              widening to float32
 // Integer atomics only: every result is bit-reproducible.
 #include "common.h"
+#include "augmath.h"
 
 namespace {
 
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void stage1_kernel(const unsigned char *__rest
     for (int i = threadIdx.x; i < kSH * kTW * 3; i += 256) {  // horizontal [1 4 6 4 1]
       const int r = i / (kTW * 3), rem = i - r * (kTW * 3);
       const unsigned char *t = tile + r * kSW * 3 + rem;
-      hrow[i] = t[0] + 4 * t[3] + 6 * t[6] + 4 * t[9] + t[12];
+      hrow[i] = blur5_row(t);
     }
   }
   __syncthreads();
@@ -67,8 +68,7 @@ __global__ __launch_bounds__(256) void stage1_kernel(const unsigned char *__rest
     for (int ch = 0; ch < 3; ch++) {
       int p;
       if (blur) {  // vertical [1 4 6 4 1]; (sum + 128) >> 8
-        const int *h = hrow + r * kTW * 3 + c * 3 + ch;
-        p = (h[0] + 4 * h[kTW * 3] + 6 * h[2 * kTW * 3] + 4 * h[3 * kTW * 3] + h[4 * kTW * 3] + 128) >> 8;
+        p = blur5_col(hrow + r * kTW * 3 + c * 3 + ch, kTW * 3);
       } else {
         p = s[((size_t)(cy + y) * Ws + cx + x) * 3 + ch];
       }
@@ -90,12 +90,6 @@ __global__ __launch_bounds__(256) void stage1_kernel(const unsigned char *__rest
 // present[b][8]: bit v set when label value v occurs anywhere in the source map (np.unique(label), utils.py:317).
 // Each lane gathers its 256-bit set in registers (16-byte loads; the word is chosen by selects, not by a runtime index),
 // the wave ORs the eight words together and one lane per wave issues the atomics.
-__device__ __forceinline__ void present_add(unsigned (&m)[8], unsigned v) {
-  const unsigned bit = 1u << (v & 31), w = v >> 5;
-#pragma unroll
-  for (int k = 0; k < 8; k++) m[k] |= (w == (unsigned)k) ? bit : 0u;
-}
-
 __global__ __launch_bounds__(256) void present_kernel(const unsigned char *__restrict__ lsrc, int n,
                                                       int *__restrict__ present) {
   __shared__ int bits[8];
@@ -332,17 +326,11 @@ AugLayout aug_layout(int B, int H, int W, int flags) {
   return L;
 }
 
-}  // namespace
-
-extern "C" size_t dl3_augment_workspace_bytes(int B, int H, int W, int flags) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return aug_layout(B, H, W, flags).total;
-}
-
-extern "C" int dl3_augment(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H,
-                           int W, int flags, const int *img_params, const int *lut, const int *warp_tab,
-                           const int *clahe_i, const float *clahe_f, int C, float *X, void *labels_out,
-                           void *workspace, size_t workspace_bytes, void *stream) {
+// present_in: the label sets of the batch from outside (dl3_augment_present), or NULL: taken from `labels` here
+int augment_run(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H, int W, int flags,
+                const int *img_params, const int *lut, const int *warp_tab, const int *clahe_i, const float *clahe_f,
+                int C, const int *present_in, float *X, void *labels_out, void *workspace, size_t workspace_bytes,
+                void *stream) {
   DL3_CHECK_ARG(images && labels && img_params && lut && X && labels_out && B > 0, "augment: bad argument");
   DL3_CHECK_ARG(H >= 3 && W >= 3 && Hs >= H && Ws >= W, "augment: output %dx%d must be at least 3x3 and fit the %dx%d "
                 "source (crops larger than the source are not supported)", H, W, Hs, Ws);
@@ -365,7 +353,7 @@ extern "C" int dl3_augment(const void *images, const void *labels, int label_dty
   hipStream_t st = (hipStream_t)stream;
   unsigned char *ws = (unsigned char *)workspace;
   unsigned char *img8 = ws + L.img, *lab8 = ws + L.lab, *yuv = ws + L.yuv, *luts = ws + L.luts;
-  int *present = (int *)(ws + L.present);
+  const int *present = present_in ? present_in : (const int *)(ws + L.present);
   const dim3 g1(dl3_cdiv(W, kTW), dl3_cdiv(H, kTH), B);
   const bool fout = !(warp || clahe);
   void *lstage = warp ? (void *)lab8 : labels_out;
@@ -378,11 +366,12 @@ extern "C" int dl3_augment(const void *images, const void *labels, int label_dty
     hipLaunchKernelGGL(k, g1, dim3(256), 0, st, (const unsigned char *)images, (const int *)labels, Hs, Ws, H, W,
                        img_params, lut, img8, X, (int *)lstage);
   }
-  if (warp) {
-    (void)hipMemsetAsync(present, 0, (size_t)B * 8 * sizeof(int), st);
+  if (warp && !present_in) {
+    int *own = (int *)(ws + L.present);
+    (void)hipMemsetAsync(own, 0, (size_t)B * 8 * sizeof(int), st);
     const int n = Hs * Ws;
     hipLaunchKernelGGL(present_kernel, dim3(min(max(dl3_cdiv(n, 256 * 64), 1), 64), B), dim3(256), 0, st,
-                       (const unsigned char *)labels, n, present);
+                       (const unsigned char *)labels, n, own);
   }
   if (clahe) {
     const int Hp = (H % kTiles || W % kTiles) ? H + kTiles - H % kTiles : H;
@@ -397,4 +386,28 @@ extern "C" int dl3_augment(const void *images, const void *labels, int label_dty
   }
   DL3_LAUNCH_CHECK("augment");
   return DL3_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dl3_augment_workspace_bytes(int B, int H, int W, int flags) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return aug_layout(B, H, W, flags).total;
+}
+
+extern "C" int dl3_augment(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H,
+                           int W, int flags, const int *img_params, const int *lut, const int *warp_tab,
+                           const int *clahe_i, const float *clahe_f, int C, float *X, void *labels_out,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  return augment_run(images, labels, label_dtype, B, Hs, Ws, H, W, flags, img_params, lut, warp_tab, clahe_i, clahe_f, C,
+                     nullptr, X, labels_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dl3_augment_present(const void *images, const void *labels, int label_dtype, int B, int Hs, int Ws, int H,
+                                   int W, int flags, const int *img_params, const int *lut, const int *warp_tab,
+                                   const int *clahe_i, const float *clahe_f, int C, const int *present, float *X,
+                                   void *labels_out, void *workspace, size_t workspace_bytes, void *stream) {
+  DL3_CHECK_ARG(present, "augment: dl3_augment_present needs the label sets");
+  return augment_run(images, labels, label_dtype, B, Hs, Ws, H, W, flags, img_params, lut, warp_tab, clahe_i, clahe_f, C,
+                     present, X, labels_out, workspace, workspace_bytes, stream);
 }

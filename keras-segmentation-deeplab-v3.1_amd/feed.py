@@ -12,6 +12,11 @@ Augmenting generators (utils.SegmentationGenerator with any augmentation keyword
 bytes plus one int32 table upload per batch (augment.tables), and consume() runs dl3_augment (blur / crop / flips / gamma
 LUT / warp / CLAHE, straight into engine.xbuf and an augmented label slot) instead of the widening copy.
 
+Generators over images of any size (device_resize=True): a slot holds the batch's images packed back to back in one uint8
+pool and the label maps in a second one, sized for the generator's largest batch (pool_px); consume() runs dl3_cv_resize
+(blur, cv2.resize or the per-image crop, the label sets of the source maps) into a uniform uint8 batch and then the same
+dl3_augment launch over it.
+
 Two device slots: while step i runs from slot i % 2 (already widened into the engine's own buffers), batch i+1 lands in the
 other one.  The compute stream waits for a slot's copy event before it reads it; the copy stream waits for the slot's
 consume event before it overwrites it.  The host never waits for a step: its only wait is for the H2D copy a slot issued
@@ -25,7 +30,7 @@ from .capi import ptr
 
 
 class BatchFeeder:
-    def __init__(self, eng, n_classes, label_dtype=np.uint8, slots=2, plan=None):
+    def __init__(self, eng, n_classes, label_dtype=np.uint8, slots=2, plan=None, pool_px=None):
         if not eng.training:
             raise ValueError("BatchFeeder feeds a training engine (images + label maps)")
         if label_dtype not in (np.uint8, np.int32):
@@ -34,11 +39,14 @@ class BatchFeeder:
         self.M = eng.logits_view.buf.M                    # label pixels per batch
         self.nx = eng.xbuf.t.numel()                      # image bytes per batch
         self.plan = plan if plan is not None and plan.active else None
+        self.front = bool(getattr(self.plan, "front", False))   # images of any size: packed pools + dl3_cv_resize
         if self.plan is not None:                         # augmenting: the slots hold the (larger) source
             if eng.B * self.plan.H * self.plan.W * 3 != self.nx:
                 raise ValueError("augmented %dx%d images do not fit the engine's input (%d floats per batch)"
                                  % (self.plan.H, self.plan.W, self.nx))
-            src = eng.B * self.plan.Hs * self.plan.Ws
+            if self.front and not pool_px:
+                raise ValueError("a feeder for images of any size needs pool_px, the pixels of the largest batch")
+            src = int(pool_px) if self.front else eng.B * self.plan.Hs * self.plan.Ws
             self.M_out, self.M, self.nx = self.M, src, 3 * src
         self.ldtype = torch.uint8 if label_dtype == np.uint8 else torch.int32
         self.lcode = capi.LABEL_U8 if label_dtype == np.uint8 else capi.LABEL_I32
@@ -51,7 +59,16 @@ class BatchFeeder:
         if self.plan is not None:
             from . import augment
             self.dlab = torch.empty(self.M_out, dtype=self.ldtype, device=dev)      # the augmented label maps
-            self.ws = torch.empty(augment.workspace_bytes(self.plan, eng.B), dtype=torch.uint8, device=dev)
+            inner = self.plan.inner if self.front else self.plan
+            self.ws = torch.empty(augment.workspace_bytes(inner, eng.B), dtype=torch.uint8, device=dev)
+            if self.front:   # the uniform batch between the front end and the chain, the label sets, the blurred pool
+                H, W = self.plan.H, self.plan.W
+                self.rimg = torch.empty(eng.B, H, W, 3, dtype=torch.uint8, device=dev)
+                self.rlab = torch.empty(eng.B, H, W, dtype=self.ldtype, device=dev)
+                self.present = torch.empty(eng.B, 8, dtype=torch.int32, device=dev)
+                fws = capi.lib().dl3_cv_resize_workspace_bytes(self.nx, int(bool(self.plan.blur)))
+                self.fws = torch.empty(int(fws), dtype=torch.uint8, device=dev)
+                self.info = [None] * self.slots
             self.dtab = [None] * self.slots
             self.htab = [None] * self.slots
             self.offs = [None] * self.slots
@@ -97,6 +114,23 @@ class BatchFeeder:
         like.numpy()[...] = np.ascontiguousarray(a).reshape(-1)
         return like
 
+    def _packed(self, slot, images, labels):
+        """images of any size: packed back to back into the slot's pinned pools (only the used prefix is meaningful)"""
+        from . import augment
+        if len(images) != self.eng.B or len(labels) != self.eng.B:
+            raise ValueError("device feed: %d images / %d label maps for a batch of %d" % (len(images), len(labels), self.eng.B))
+        for i, l in zip(images, labels):
+            self._checked(i, self.hx[slot], "images")
+            self._checked(l, self.hl[slot], "labels")
+            if np.asarray(l).dtype != self.hl[slot].numpy().dtype:
+                raise ValueError("device feed: this feeder was built for %s label maps, got %s"
+                                 % (self.hl[slot].numpy().dtype, np.asarray(l).dtype))
+        px = sum(int(np.shape(i)[0]) * int(np.shape(i)[1]) for i in images)
+        if px > self.M:
+            raise ValueError("device feed: a batch of %d pixels does not fit the slots of %d" % (px, self.M))
+        augment.pack_pools(images, labels, self.hx[slot].numpy(), self.hl[slot].numpy())
+        return self.hx[slot], self.hl[slot]
+
     def stage(self, slot, images, labels, params=None):
         """enqueue batch (images uint8 [B,H,W,3], labels [B,H,W] or [B,HW]; params: the augment.ImageParams of every
         image when augmenting) for `slot` on the copy stream"""
@@ -104,13 +138,20 @@ class BatchFeeder:
             raise ValueError("device feed: an augmenting feeder takes (images, labels, params), a plain one (images, labels)")
         if self._used[slot]:
             self.ready[slot].synchronize()   # (the slot's previous H2D copy, two steps old, has left its pinned buffer)
-        hx, hl = self._pinned(images, self.hx[slot], "images"), self._pinned(labels, self.hl[slot], "labels")
-        assert hx.numel() == self.nx and hl.numel() == self.M, (hx.numel(), self.nx, hl.numel(), self.M)
+        if self.front:
+            hx, hl = self._packed(slot, images, labels)
+        else:
+            hx, hl = self._pinned(images, self.hx[slot], "images"), self._pinned(labels, self.hl[slot], "labels")
+            assert hx.numel() == self.nx and hl.numel() == self.M, (hx.numel(), self.nx, hl.numel(), self.M)
         if params is not None:
             from . import augment
             if len(params) != self.eng.B:
                 raise ValueError("device feed: %d augmentation parameter sets for %d images" % (len(params), self.eng.B))
-            tab, self.offs[slot] = augment.tables(self.plan, params)
+            if self.front:
+                tab, self.offs[slot], info = augment.batch_tables(self.plan, [np.shape(i)[:2] for i in images], params)
+                self.info[slot] = info._replace(pool_px=self.M)
+            else:
+                tab, self.offs[slot] = augment.tables(self.plan, params)
             if self.htab[slot] is None or self.htab[slot].numel() != tab.size:
                 self.htab[slot] = torch.empty(tab.size, dtype=torch.int32).pin_memory()
                 self.dtab[slot] = torch.empty(tab.size, dtype=torch.int32, device=self.eng.device)
@@ -135,8 +176,14 @@ class BatchFeeder:
         else:
             from . import augment
             B, (Hs, Ws) = eng.B, (self.plan.Hs, self.plan.Ws)
-            augment.launch(self.plan, self.dtab[slot], self.offs[slot], self.dx[slot].view(B, Hs, Ws, 3),
-                           self.dl[slot].view(B, Hs, Ws), self.C, eng.xbuf.t, self.dlab, self.ws, st.cuda_stream)
+            if self.front:
+                augment.launch_front(self.info[slot], self.dtab[slot], self.offs[slot], self.dx[slot], self.dl[slot],
+                                     self.rimg, self.rlab, self.present, self.fws, st.cuda_stream)
+                augment.launch(self.plan.inner, self.dtab[slot], self.offs[slot], self.rimg, self.rlab, self.C,
+                               eng.xbuf.t, self.dlab, self.ws, st.cuda_stream, present=self.present)
+            else:
+                augment.launch(self.plan, self.dtab[slot], self.offs[slot], self.dx[slot].view(B, Hs, Ws, 3),
+                               self.dl[slot].view(B, Hs, Ws), self.C, eng.xbuf.t, self.dlab, self.ws, st.cuda_stream)
             lab, M = self.dlab, self.M_out
         capi.call("dl3_prepare_targets", ptr(lab), self.lcode, eng.B, M // eng.B, self.C, ptr(eng.labels),
                   ptr(eng.sweights), ptr(self.hist), st.cuda_stream)

@@ -916,7 +916,8 @@ class Model:
         — what cv2 decodes, before SegmentationGenerator.__getitem__ turns it into float tensors (utils.py:375-402): the
         batch crosses PCIe as bytes on a copy stream while the previous step runs, and X / Y / SW are produced on the device
         (feed.BatchFeeder: widening copy + dl3_prepare_targets).  A utils.SegmentationGenerator is read through its
-        raw_batch(i): with augmentation on, the feeder runs dl3_augment on the device instead of the widening copy.
+        raw_batch(i): with augmentation on, the feeder runs dl3_augment on the device instead of the widening copy; a
+        device_resize generator hands over images of any size and the feeder runs dl3_cv_resize in front of it (one GPU).
         validation_data=generator | (x, y[, sw]), validation_steps=, callbacks=[...]: as in fit(); validation batches come
         from the generator's __getitem__ (also with device_feed=True: the feed serves the training half).
         Under distribute() (utils.py:209-211 + :231-241): global_batch=True — the generator yields the GLOBAL batch and each
@@ -956,6 +957,11 @@ class Model:
         # utils.SegmentationGenerator: raw_batch() gives the source bytes (+ augmentation parameters) of a batch
         raw = hasattr(generator, "raw_batch")
         plan = getattr(generator, "plan", None) if raw else None
+        # device_resize generators hand over LISTS of images of any size; the feeder packs them (feed.BatchFeeder)
+        ragged = bool(getattr(plan, "front", False))
+        if ragged and dp is not None:
+            raise ValueError("fit_generator(device_feed=True): a device_resize generator (images of any size) cannot be "
+                             "sharded under distribute(); resize on the host first or train on one GPU")
         for ep in range(epochs):
             if ses:
                 ses.epoch_begin(ep)
@@ -972,6 +978,9 @@ class Model:
                     else:
                         item = generator[i] if hasattr(generator, "__getitem__") else next(generator)
                         X, L, P = item[0], item[1], None
+                    if ragged:
+                        yield (X, L, P)
+                        continue
                     X, L = np.asarray(X), np.asarray(L)
                     if dp is not None and global_batch:
                         # the rank's contiguous shard of the global batch (the remainder of a batch that does not divide goes
@@ -986,18 +995,20 @@ class Model:
             first = next(it, None)
             if first is None:
                 break
-            eng = self._engine(first[0].shape[0], True, **ekw)
+            eng = self._engine(len(first[0]), True, **ekw)
             if dp is not None:
                 self._dp_sync_weights(eng)
-            key = (id(eng), first[1].dtype.str)
+            ldt = first[1][0].dtype if ragged else first[1].dtype
+            key = (id(eng), ldt.str)
             if key not in feeders:
-                feeders[key] = BatchFeeder(eng, C, np.uint8 if first[1].dtype == np.uint8 else np.int32, plan=plan)
+                feeders[key] = BatchFeeder(eng, C, np.uint8 if ldt == np.uint8 else np.int32, plan=plan,
+                                           pool_px=generator.pool_pixels if ragged else None)
 
             def chain():
                 yield first
                 for b in it:
-                    if b[0].shape[0] != eng.B:
-                        raise ValueError("device_feed needs batches of one size (got %d after %d)" % (b[0].shape[0], eng.B))
+                    if len(b[0]) != eng.B:
+                        raise ValueError("device_feed needs batches of one size (got %d after %d)" % (len(b[0]), eng.B))
                     yield b
 
             def step():

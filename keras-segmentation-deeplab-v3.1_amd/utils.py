@@ -8,7 +8,8 @@ device) and `Jaccard_from_counts` / `accuracy_from_counts` (N3, metrics from dl3
 `do_crf` (N4) is the host hook with the reference's parameters (it needs the optional pydensecrf package);
 `do_crf(..., backend="device")` runs the exact mean-field inference of the same model on the GPU (crf.py, csrc/crf.hip).
 The cv2 augmentation chain (utils.py:319-365) runs on the device (augment.py, dl3_augment) behind
-SegmentationGenerator's augmentation keywords and SegModel.create_generators.
+SegmentationGenerator's augmentation keywords and SegModel.create_generators; with device_resize=True so does cv2.resize
+over images of any size (dl3_cv_resize).
 Out of scope by the SURVEY §8 contract: image file I/O, plotting.
 """
 import numpy as np
@@ -231,33 +232,76 @@ class SegmentationGenerator:
     any of them on, images must be uint8, the per-image parameters come from one `random.Random(seed)` in the
     reference's call order (augment.Plan.draw; `on_epoch_end` shuffles with the same stream, as the reference's global
     `random` does), and the chain runs on the device (dl3_augment): X comes back as host float32, Y / SW stay on the
-    device.  `raw_batch(i)` hands the same batch to the device feed before augmentation."""
+    device.  `raw_batch(i)` hands the same batch to the device feed before augmentation.
+
+    device_resize=True (off by default): `images` / `labels` may be lists of per-image arrays of different sizes, or arrays
+    of any one size.  resize_shape resizes every image as cv2.resize does (INTER_LINEAR, the label map INTER_NEAREST);
+    crop_shape follows _random_crop per image (utils.py:411-423): an image larger than the crop both ways is cropped at a
+    drawn origin, any other is resized to crop_shape without a draw.  Blur, resize and crop run in dl3_cv_resize, the
+    rest of the chain in dl3_augment over the uniform batch; with every other flag off X is the widened resized image."""
 
     def __init__(self, images, labels, n_classes=21, batch_size=1, seed=7, shuffle=True, resize_shape=None,
                  crop_shape=None, horizontal_flip=False, vertical_flip=False, blur=0, brightness=0.0, rotation=0.0,
-                 zoom=0.0, do_ahisteq=False):
+                 zoom=0.0, do_ahisteq=False, device_resize=False):
         import random
         from . import augment
-        self.images = np.asarray(images)
-        self.labels = np.asarray(labels)
-        if self.images.ndim != 4 or self.images.shape[-1] != 3 or len(self.images) != len(self.labels):
-            raise Exception("images must be [N,H,W,3] and labels [N,H,W]")
         self.n_classes = int(n_classes)
         self.batch_size = int(batch_size)
         self.shuffle = shuffle
         self._rng = np.random.RandomState(seed)
+        self.random = random.Random(seed)
+        self.device_resize = bool(device_resize)
+        if self.device_resize:
+            self._init_any_size(images, labels, resize_shape, crop_shape, horizontal_flip, vertical_flip, blur, brightness,
+                                rotation, zoom, do_ahisteq)
+            return
+        self.images = np.asarray(images)
+        self.labels = np.asarray(labels)
+        if self.images.ndim != 4 or self.images.shape[-1] != 3 or len(self.images) != len(self.labels):
+            raise Exception("images must be [N,H,W,3] and labels [N,H,W]")
         self.order = np.arange(len(self.images))
         self.plan = augment.Plan(self.images.shape[1:3], resize_shape, crop_shape, horizontal_flip, vertical_flip, blur,
                                  brightness, rotation, zoom, do_ahisteq)
-        self.random = random.Random(seed)
         if self.plan.active:
-            if self.images.dtype != np.uint8:
-                raise ValueError("augmentation reads decoded uint8 images, got %s" % self.images.dtype)
-            if self.labels.dtype not in (np.uint8, np.int32):
-                raise ValueError("augmentation reads uint8 / int32 label maps, got %s" % self.labels.dtype)
-            if self.plan.warp and self.labels.dtype != np.uint8:
-                raise ValueError("rotation / zoom warp the label map as uint8 (cv2.warpAffine, utils.py:353): "
-                                 "int32 label maps cannot be warped")
+            self._check_dtypes(self.images.dtype, self.labels.dtype)
+
+    def _check_dtypes(self, idt, ldt):
+        if idt != np.uint8:
+            raise ValueError("augmentation reads decoded uint8 images, got %s" % idt)
+        if ldt not in (np.uint8, np.int32):
+            raise ValueError("augmentation reads uint8 / int32 label maps, got %s" % ldt)
+        if self.plan.warp and ldt != np.uint8:
+            raise ValueError("rotation / zoom warp the label map as uint8 (cv2.warpAffine, utils.py:353): "
+                             "int32 label maps cannot be warped")
+
+    def _init_any_size(self, images, labels, *opts):
+        """device_resize=True: per-image arrays of any size (a list, or a uniform array); cv2.resize / the per-image crop
+        of utils.py:322-327 run on the device (dl3_cv_resize) in front of the rest of the chain"""
+        from . import augment
+        self.images = [np.asarray(i) for i in images]
+        self.labels = [np.asarray(l) for l in labels]
+        if not self.images or len(self.images) != len(self.labels):
+            raise ValueError("device_resize: one label map per image, got %d images and %d maps"
+                             % (len(self.images), len(self.labels)))
+        for n, (i, l) in enumerate(zip(self.images, self.labels)):
+            if i.ndim != 3 or i.shape[2] != 3 or l.shape != i.shape[:2] or not i.size:
+                raise ValueError("device_resize: image %d is %r with a label map %r; images are [H,W,3], maps [H,W]"
+                                 % (n, i.shape, l.shape))
+        self.sizes = [i.shape[:2] for i in self.images]
+        self.order = np.arange(len(self.images))
+        same = len(set(self.sizes)) == 1
+        self.plan = augment.Plan(self.sizes[0] if same else None, *opts, device_resize=True)
+        idt, ldt = set(i.dtype for i in self.images), set(l.dtype for l in self.labels)
+        if len(idt) != 1 or len(ldt) != 1:
+            raise ValueError("device_resize: images and label maps must each have one dtype, got %s / %s"
+                             % (sorted(map(str, idt)), sorted(map(str, ldt))))
+        self._check_dtypes(idt.pop(), ldt.pop())
+
+    @property
+    def pool_pixels(self):
+        """device_resize: the pixels a batch can hold at most — the batch_size largest images (what the feeder's slots and
+        this generator's own device buffers are sized for)"""
+        return int(sum(sorted((h * w for h, w in self.sizes), reverse=True)[:self.batch_size]))
 
     def __len__(self):
         return len(self.images) // self.batch_size
@@ -271,10 +315,47 @@ class SegmentationGenerator:
         """(uint8 images [B,Hs,Ws,3], label maps [B,Hs,Ws], params) of batch i before augmentation; params is the list
         of augment.ImageParams drawn for it (None when no augmentation is on)"""
         idx = self._index(i)
+        if self.device_resize:    # lists of per-image arrays; each draw sees its image's size
+            return ([self.images[j] for j in idx], [self.labels[j] for j in idx],
+                    [self.plan.draw(self.random, self.sizes[j]) for j in idx])
         params = [self.plan.draw(self.random) for _ in idx] if self.plan.active else None
         return self.images[idx], self.labels[idx], params
 
+    def _getitem_any_size(self, i):
+        import torch
+        from . import augment
+        images, labels, params = self.raw_batch(i)
+        plan, B = self.plan, len(params)
+        tab, offs, info = augment.batch_tables(plan, [im.shape[:2] for im in images], params)
+        info = info._replace(pool_px=self.pool_pixels)
+        ldt = torch.uint8 if labels[0].dtype == np.uint8 else torch.int32
+        if getattr(self, "_dev", None) is None:
+            n = info.pool_px
+            # device buffers of one batch, allocated once and reused by every batch of this generator
+            self._dev = dict(img=torch.empty(3 * n, dtype=torch.uint8, device="cuda"),
+                             lab=torch.empty(n, dtype=ldt, device="cuda"),
+                             fws=torch.empty(augment.front_workspace_bytes(info._replace(blur_any=int(bool(plan.blur)))),
+                                             dtype=torch.uint8, device="cuda"),
+                             rimg=torch.empty(B, plan.H, plan.W, 3, dtype=torch.uint8, device="cuda"),
+                             rlab=torch.empty(B, plan.H, plan.W, dtype=ldt, device="cuda"),
+                             present=torch.empty(B, 8, dtype=torch.int32, device="cuda"),
+                             X=torch.empty(B, plan.H, plan.W, 3, dtype=torch.float32, device="cuda"),
+                             L=torch.empty(B, plan.H * plan.W, dtype=ldt, device="cuda"),
+                             ws=torch.empty(augment.workspace_bytes(plan.inner, B), dtype=torch.uint8, device="cuda"))
+        d = self._dev
+        ipool, lpool = augment.pack_pools(images, labels)
+        d["img"][:ipool.size].copy_(torch.from_numpy(ipool))
+        d["lab"][:lpool.size].copy_(torch.from_numpy(lpool))
+        dtab = torch.from_numpy(tab).cuda()
+        augment.launch_front(info, dtab, offs, d["img"], d["lab"], d["rimg"], d["rlab"], d["present"], d["fws"])
+        augment.launch(plan.inner, dtab, offs, d["rimg"], d["rlab"], self.n_classes, d["X"], d["L"], d["ws"],
+                       present=d["present"])
+        Y, SW = prepare_targets(d["L"], self.n_classes)
+        return d["X"].cpu().numpy(), Y, {"pred_mask": SW}
+
     def __getitem__(self, i):
+        if self.device_resize:
+            return self._getitem_any_size(i)
         if not self.plan.active:
             idx = self._index(i)
             X = np.ascontiguousarray(self.images[idx], dtype=np.float32)
@@ -369,12 +450,14 @@ class SegModel:
 
     def create_generators(self, crop_shape=False, mode="train", do_ahisteq=True, n_classes=21, horizontal_flip=True,
                           vertical_flip=False, blur=False, with_bg=True, brightness=0.1, rotation=5.0, zoom=0.1,
-                          validation_split=.2, seed=7, images=None, labels=None):
+                          validation_split=.2, seed=7, images=None, labels=None, device_resize=False):
         """utils.py:216-226 over in-memory arrays (this package reads no files): `images` uint8 [N,H,W,3] in cv2's BGR
         order at the model's size (or larger, with crop_shape), `labels` uint8 / int32 [N,H,W].  mode 'train' /
         'validation' split as the reference does (utils.py:268-276): np.random.seed(seed); the first
         round(N * validation_split) of permutation(N) validate, the sorted rest trains.  with_bg is accepted and ignored,
-        as in the reference."""
+        as in the reference.  device_resize=True: `images` / `labels` are lists of per-image arrays of any sizes (or arrays
+        of any one size) and every image is resized to the model's size — or cropped / resized to crop_shape, per image —
+        on the device, as the reference's cv2.resize does (utils.py:322-327)."""
         if mode not in ("train", "validation"):
             raise ValueError("create_generators: mode %r is not supported (the reference's 'test' mode reads the test "
                              "JPEG folder; this package reads no files)" % (mode,))
@@ -382,12 +465,18 @@ class SegModel:
             raise ValueError("create_generators: pass the decoded data as images= (uint8 [N,H,W,3], BGR) and labels= "
                              "(uint8 / int32 [N,H,W]); reading the dataset folder %r (JPEG decode) is out of scope"
                              % (self.mainpath,))
-        images, labels = np.asarray(images), np.asarray(labels)
+        if not device_resize:
+            images, labels = np.asarray(images), np.asarray(labels)
         n = len(images)
         x = np.random.RandomState(seed).permutation(n)[:round(n * validation_split)]
         if mode == "train":
             x = np.setxor1d(x, np.arange(n))
-        return SegmentationGenerator(images[x], labels[x], n_classes=n_classes, batch_size=self.batch_size, seed=seed,
+        if device_resize:
+            images, labels = [images[j] for j in x], [labels[j] for j in x]
+        else:
+            images, labels = images[x], labels[x]
+        return SegmentationGenerator(images, labels, n_classes=n_classes, batch_size=self.batch_size, seed=seed,
+                                     device_resize=device_resize,
                                      resize_shape=self.sz[::-1], crop_shape=crop_shape, horizontal_flip=horizontal_flip,
                                      vertical_flip=vertical_flip, blur=blur, brightness=brightness, rotation=rotation,
                                      zoom=zoom, do_ahisteq=do_ahisteq)

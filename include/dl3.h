@@ -366,6 +366,30 @@ int dl3_upsample_softmax_xent_fold(const float *logits_lo, const float *labels, 
                                    int C, void *stream);
 int dl3_resize_bilinear_bwd_rows(const float *xfold, float *dx, int lddx, int N, int Hi, int Wi, int Ho, int C,
                                  int accumulate, void *stream);
+/* ---- hard-example mining in front of the loss kernels above (csrc/mine.hip; DeepLab's top_k_percent_pixels, restated
+ * from memory of deeplab/utils/train_utils.py): the step trains on the k largest per-pixel losses.
+ * v[m] = w[m] * -log clip(p[m,label], 1e-7, 1-1e-7) in fp32, +0 where the label is void or the product is not > 0;
+ * weights nullable (w = 1).  One source per training form: materialised logits [M,C] (any C), the low-resolution
+ * logits in front of the final resize (TF's stated weight, as dl3_upsample_softmax_xent's loss; C <= 32), the
+ * UNshuffled Subpixel output u [N,H,W,C*r*r] (labels / weights / v at [N,H*r,W*r]; C <= 32). */
+int dl3_pixel_xent_plain(const float *logits, const float *labels, const float *weights, float *v, int M, int C,
+                         void *stream);
+int dl3_pixel_xent_bilinear(const float *logits_lo, const float *labels, const float *weights, float *v, int N, int Hi,
+                            int Wi, int Ho, int Wo, int C, void *stream);
+int dl3_pixel_xent_shuffle(const float *u, const float *labels, const float *weights, float *v, int N, int H, int W,
+                           int C, int r, void *stream);
+/* *k = min(N, trunc(pct * N)), pct = p if S == 0 else ratio*p + (1 - ratio), ratio = min(1, s/S), s = *step (nullable:
+ * 0) — every operation one rounded float32 operation; *tau = the k-th largest of v[N] (v >= 0: a radix select over the
+ * bit patterns, +inf and denormals are ordinary values; k == 0: +inf, and dl3_mine_weights selects nothing).
+ * ws: dl3_topk_workspace_bytes(N) bytes, zeroed by the call itself; deterministic (integer atomics only). */
+size_t dl3_topk_workspace_bytes(int N);
+int dl3_topk_threshold(const float *v, int N, float p, int S, const unsigned long long *step, void *ws, size_t ws_bytes,
+                       int *k, float *tau, void *stream);
+/* w_out[m] = weights[m] (nullable: 1) where v[m] >= *tau and v[m] > 0 (and *k > 0), else 0: ties at tau are all kept;
+ * *nnz_out = their number, counted in integers and converted once.  ws is the workspace the dl3_topk_threshold call in
+ * front of it used (it holds the counter, zeroed there). */
+int dl3_mine_weights(const float *v, const float *weights, const float *tau, const int *k, float *w_out, float *nnz_out,
+                     void *ws, int N, void *stream);
 /* out[i] = sum_p partial[p][i]  (fixed order) */
 int dl3_reduce_partials(const float *partial, int P, int n, float *out, void *stream);
 /* m folds in one launch, each bit-identical to its own dl3_reduce_partials call.  desc (device, int64 [m][5]): partial

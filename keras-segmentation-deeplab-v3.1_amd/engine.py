@@ -23,7 +23,7 @@ import torch
 
 from . import capi
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
-from .graph import raw_pixels
+from .graph import check_mining, raw_pixels
 
 _ACT = {"relu": ACT_RELU, "relu6": ACT_RELU6}
 V_SCALE, V_SHIFT, V_MEAN, V_INVSTD, V_CA, V_CB, V_CC, V_NEGMEAN = range(8)
@@ -244,7 +244,8 @@ class View:
 
 class Engine:
     def __init__(self, model, batch, training, bn_mode="batch", dropout=True, seed=2, device=None, use_graph=True,
-                 dw_impl=IMPL_AUTO, rank=None, bn_variance="keras224", external_nnz=False, opt_trainable=None, bn_update=None):
+                 dw_impl=IMPL_AUTO, rank=None, bn_variance="keras224", external_nnz=False, opt_trainable=None, bn_update=None,
+                 mining=None):
         if not torch.cuda.is_available():
             raise capi.DL3Error("the dl3 engine needs a GPU (HIP device); there is no CPU fallback")
         self.lib = capi.lib()
@@ -265,6 +266,9 @@ class Engine:
         # the tower outputs and evaluates ONE loss, utils.py:209-211) — the host writes it before each step instead of
         # the in-graph dl3_count_nonzero of the local shard (Engine.set_nnz)
         self.external_nnz = bool(external_nnz)
+        # hard-example mining: (top_k_percent_pixels, hard_example_mining_step) — the step trains on the k
+        # largest per-pixel losses, k from the schedule and the device-side step counter; None / p == 1: today's plan
+        self.mining = check_mining(mining) if training else None
         self.device = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
         self.use_graph = use_graph
         self.fold_tail = True   # the loss kernel folds its gradient rows onto the low-resolution columns (the full-resolution dlogits never exist)
@@ -319,6 +323,8 @@ class Engine:
         self._main = Plan(self, self._run_main)
         self._keep = []
         self.drop_step = torch.zeros(1, dtype=torch.int64, device=self.device)  # device-side step number (dropout)
+        # device-side count of the steps taken (the mining schedule's s: launch arguments are frozen inside the hipGraph)
+        self.mine_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._plan_channels()
         self._build_params()
         self._lower()
@@ -326,6 +332,8 @@ class Engine:
             self._lower_backward()
             if self.dropout:
                 self.op(self.ops_bwd, "dl3_counter_add", self.drop_step.data_ptr(), 1)
+            if self.mining:
+                self.op(self.ops_bwd, "dl3_counter_add", self.mine_step.data_ptr(), 1)
         self.scratch = self.empty(max(self.scratch_bytes // 4, 4))
         for op in self._scratch_users:
             op[2][op[3]] = self.scratch.data_ptr()
@@ -976,21 +984,67 @@ class Engine:
             if own or any(b.requires_grad for b in ins):
                 u.outv.buf.requires_grad = True   # (a Concatenate buffer: any of its producers)
 
+    MINING_OPS = ("dl3_pixel_xent_plain", "dl3_pixel_xent_bilinear", "dl3_pixel_xent_shuffle", "dl3_topk_threshold",
+                  "dl3_mine_weights")
+    MINE_WS_COUNT = 4   # S_COUNT of the workspace enum in csrc/mine.hip: the kept pixels as an integer (32-bit words)
+
+    def _lower_mining(self, M, C, count_dst):
+        """the mining front of the loss kernel: v, (k, tau), (w', n').  -> the pointer the loss kernel takes as weights"""
+        p, S = self.mining
+        v = self.logits_view
+        self.mine_v, self.mine_w = self.empty(M), self.zeros(M)
+        self.mine_tau = self.zeros(4)
+        self.mine_k = torch.zeros(4, dtype=torch.int32, device=self.device)
+        nws = int(self.lib.dl3_topk_workspace_bytes(M))
+        self.mine_ws = torch.zeros(nws // 4, dtype=torch.int32, device=self.device)
+        self._mine_count = count_dst
+        args = (ptr(self.labels), ptr(self.sweights), ptr(self.mine_v))
+        if self.fused_shuffle is not None:
+            su = self.fused_shuffle
+            ub = su.inv.buf
+            self.op(self.ops_fwd, "dl3_pixel_xent_shuffle", su.inv.p(), *args, self.B, ub.H, ub.W, su.co, su.r)
+        elif self.fused_tail is not None:
+            lo = self.fused_tail.inv
+            self.op(self.ops_fwd, "dl3_pixel_xent_bilinear", lo.p(), *args, self.B, lo.buf.H, lo.buf.W, v.buf.H, v.buf.W, C)
+        else:
+            self.op(self.ops_fwd, "dl3_pixel_xent_plain", ptr(v.buf.t), *args, M, C)
+        self.op(self.ops_fwd, "dl3_topk_threshold", ptr(self.mine_v), M, p, S, self.mine_step.data_ptr(),
+                self.mine_ws.data_ptr(), nws, self.mine_k.data_ptr(), ptr(self.mine_tau))
+        self.op(self.ops_fwd, "dl3_mine_weights", ptr(self.mine_v), ptr(self.sweights), ptr(self.mine_tau),
+                self.mine_k.data_ptr(), ptr(self.mine_w), count_dst, self.mine_ws.data_ptr(), M)
+        return ptr(self.mine_w)
+
+    def mining_record(self):
+        """(v, w', tau, k, n') of the last step, read back (test-facing): the per-pixel losses [B*H*W], the mined weights,
+        the threshold, the number of pixels asked for and the number kept"""
+        if not self.mining:
+            raise ValueError("mining_record: this engine was lowered without mining")
+        torch.cuda.current_stream().synchronize()
+        ws = self.mine_ws.cpu().numpy()
+        return (self.mine_v.cpu().numpy(), self.mine_w.cpu().numpy(), float(self.mine_tau[0].item()),
+                int(self.mine_k[0].item()), int(ws[self.MINE_WS_COUNT]))
+
     def _lower_backward(self):
         self._prune_gradients()
         v = self.logits_view
         buf = v.buf
         M, C = buf.M, v.C
         # loss + dlogits (first and only contribution to the logits buffer)
-        self.op(self.ops_fwd, "dl3_count_nonzero", ptr(self.sweights), M,
-                (self.grads.data_ptr() + 4 * self.tail) if self.external_nnz else ptr(self.nnz))
+        count_dst = (self.grads.data_ptr() + 4 * self.tail) if self.external_nnz else ptr(self.nnz)
+        if self.mining:
+            # three launches in place of the count: per-pixel losses v from the source the loss kernel below reads, k
+            # and the k-th largest v, then the mined weights w' and their count n' where count(w != 0) goes today
+            wsrc = self._lower_mining(M, C, count_dst)
+        else:
+            self.op(self.ops_fwd, "dl3_count_nonzero", ptr(self.sweights), M, count_dst)
+            wsrc = ptr(self.sweights)
         if self.fused_shuffle is not None:
             su = self.fused_shuffle
             ub = su.inv.buf
             ub.grad = self.empty(ub.M * ub.ld)
             self.lossP = self.lib.dl3_shuffle_xent_partials(self.B, ub.H, ub.W, su.co, su.r)
             self.loss_part = self.zeros(self.lossP)
-            self.op(self.ops_fwd, "dl3_shuffle_softmax_xent", su.inv.p(), ptr(self.labels), ptr(self.sweights), ptr(self.nnz),
+            self.op(self.ops_fwd, "dl3_shuffle_softmax_xent", su.inv.p(), ptr(self.labels), wsrc, ptr(self.nnz),
                     ptr(ub.grad), ptr(self.loss_part), self.B, ub.H, ub.W, su.co, su.r)
             su.fused = True
         elif self.fused_tail is not None and ((buf.W + 2 * self.fused_tail.inv.buf.W) * C + 2 * buf.W) * 4 <= 65536 and self.fold_tail:
@@ -1000,17 +1054,17 @@ class Engine:
             self.lossP = self.lib.dl3_xent_fold_partials(self.B, buf.H)
             self.loss_part = self.zeros(self.lossP)
             self.fused_tail.xfold = self.empty(self.B * buf.H * lo.buf.W * C)
-            self.op(self.ops_fwd, "dl3_upsample_softmax_xent_fold", lo.p(), ptr(self.labels), ptr(self.sweights),
+            self.op(self.ops_fwd, "dl3_upsample_softmax_xent_fold", lo.p(), ptr(self.labels), wsrc,
                     ptr(self.nnz), ptr(self.fused_tail.xfold), ptr(self.loss_part), self.B, lo.buf.H, lo.buf.W, buf.H,
                     buf.W, C)
         elif self.fused_tail is not None:
             buf.grad = self.empty(M * buf.ld)
             lo = self.fused_tail.inv
-            self.op(self.ops_fwd, "dl3_upsample_softmax_xent", lo.p(), ptr(self.labels), ptr(self.sweights),
+            self.op(self.ops_fwd, "dl3_upsample_softmax_xent", lo.p(), ptr(self.labels), wsrc,
                     ptr(self.nnz), None, ptr(buf.grad), ptr(self.loss_part), self.B, lo.buf.H, lo.buf.W, buf.H, buf.W, C)
         else:
             buf.grad = self.empty(M * buf.ld)
-            self.op(self.ops_fwd, "dl3_softmax_xent", ptr(buf.t), ptr(self.labels), ptr(self.sweights), ptr(self.nnz),
+            self.op(self.ops_fwd, "dl3_softmax_xent", ptr(buf.t), ptr(self.labels), wsrc, ptr(self.nnz),
                     None, ptr(buf.grad), ptr(self.loss_part), M, C)
         self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP, 1, ptr(self.loss))
         buf.done = 1
@@ -1588,6 +1642,11 @@ class Engine:
         self.adam_m.copy_(other.adam_m)
         self.adam_v.copy_(other.adam_v)
         self.drop_step.copy_(other.drop_step)
+        # the mining ramp continues with the optimizer's clock (an engine lowered without mining did not count its steps)
+        if other.mining:
+            self.mine_step.copy_(other.mine_step)
+        else:
+            self.mine_step.fill_(int(other.iteration))
         self.iteration = other.iteration
 
     def train_step(self, x, y, sw=None, opt=None, comm=None, lazy=False):

@@ -17,6 +17,21 @@ _uids = collections.defaultdict(int)
 _rng = np.random.default_rng(0)
 
 
+def check_mining(mining):
+    """(top_k_percent_pixels, hard_example_mining_step) -> (float p, int S), or None where mining is off (None, p == 1);
+    ValueError for p outside (0, 1], a negative or non-integer S"""
+    if mining is None:
+        return None
+    p, S = mining
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.floating, np.integer)) or not 0.0 < float(p) <= 1.0:
+        raise ValueError("top_k_percent_pixels must be a number in (0, 1], got %r" % (p,))
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or int(S) < 0:
+        raise ValueError("hard_example_mining_step must be an integer >= 0, got %r" % (S,))
+    if float(p) == 1.0:
+        return None
+    return float(p), int(S)
+
+
 def raw_pixels(x):
     """raw 0-255 pixels as the package takes them: a device tensor or a uint8 array (decoded images) as it is, anything
     else as a float32 array (the reference's arrays)"""
@@ -500,6 +515,8 @@ class Model:
         prev, prev_obj = self._train_eng, getattr(self, "_opt_object", None)
         keep = prev is not None and optimizer is not None and optimizer is prev_obj and not isinstance(optimizer, (dict, str))
         self._carry_iterations = (int(prev.iteration), prev.drop_step.clone()) if keep else None
+        # ... and so does the mining ramp (its device step counter, or the iteration count of an engine that did not mine)
+        self._carry_mine_step = (prev.mine_step.clone() if prev.mining else int(prev.iteration)) if keep else None
         self._opt_object = optimizer
         self._train_eng = None
 
@@ -537,16 +554,31 @@ class Model:
                               UserWarning, stacklevel=4)
         return self._collected_trainable, self._update_flags, ("compiled", self._compile_gen)
 
-    def _engine(self, batch, training, **kw):
-        """engine for (batch, mode); weights travel through the host master copies when the active engine changes, the
-        optimizer state (Adam moments, iteration, dropout step) moves device-to-device between training engines, and
-        the least recently used engines beyond MAX_ENGINES are dropped (each one owns a full activation arena)."""
-        from .engine import Engine
+    def _mining(self):
+        """(p, S) of a compile(loss=utils.sparse_crossentropy_top_k(...)) that mines, else None (any other loss, p == 1)"""
+        loss = (getattr(self, "_compiled", None) or {}).get("loss")
+        return getattr(loss, "mining", None)
+
+    def _engine_key(self, batch, training, kw):
+        """(cache key, constructor keywords) of the engine for (batch, mode, keywords): host-only.  A training engine's
+        key carries the trainable flags and, through the keywords, the mining settings of the compiled loss — a plan
+        lowered for one setting is never replayed for another; a loss that does not mine adds nothing to either."""
+        kw = dict(kw)
+        if training and "mining" not in kw and self._mining() is not None:
+            kw["mining"] = self._mining()
         key = (int(batch), bool(training), tuple(sorted(kw.items())))
         if training:
             flags = self._training_flags()
             kw = dict(kw, opt_trainable=flags[0], bn_update=flags[1])
             key = key + (flags[2],)
+        return key, kw
+
+    def _engine(self, batch, training, **kw):
+        """engine for (batch, mode); weights travel through the host master copies when the active engine changes, the
+        optimizer state (Adam moments, iteration, dropout step) moves device-to-device between training engines, and
+        the least recently used engines beyond MAX_ENGINES are dropped (each one owns a full activation arena)."""
+        from .engine import Engine
+        key, kw = self._engine_key(batch, training, kw)
         eng = self._engines.pop(key, None)
         active = getattr(self, "_active", None)
         if eng is not active and active is not None:
@@ -567,7 +599,11 @@ class Model:
                 eng.adam_m.zero_()
                 eng.adam_v.zero_()
                 eng.drop_step.copy_(drop)
-                self._carry_iterations = None
+                if isinstance(self._carry_mine_step, int):
+                    eng.mine_step.fill_(self._carry_mine_step)
+                else:
+                    eng.mine_step.copy_(self._carry_mine_step)
+                self._carry_iterations = self._carry_mine_step = None
             self._train_eng = eng
         while len(self._engines) > self.MAX_ENGINES:
             k0 = next(iter(self._engines))

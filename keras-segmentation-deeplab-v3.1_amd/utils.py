@@ -40,6 +40,46 @@ def sparse_crossentropy_ignoring_last_label(y_true, y_pred):
     return out
 
 
+class sparse_crossentropy_top_k:
+    """Loss object for Model.compile(loss=...): sparse_crossentropy_ignoring_last_label with online hard-example mining
+    (DeepLab's train_utils, restated from memory).  The step trains on the `top_k_percent_pixels` largest
+    per-pixel losses w*l of the batch, chosen on the device; with hard_example_mining_step = S > 0 the share ramps down
+    from 100 % to top_k_percent_pixels over the first S optimizer updates.  The loss is the sum of the kept losses over
+    the number of kept non-zero ones; ties at the threshold are all kept.  top_k_percent_pixels = 1.0 switches mining
+    off (the plain loss, bit for bit).  Calling the object on host arrays returns the per-pixel losses, as the plain
+    marker does.  Evaluation and prediction are not mined."""
+
+    def __init__(self, top_k_percent_pixels, hard_example_mining_step=0):
+        G.check_mining((top_k_percent_pixels, hard_example_mining_step))   # ValueError
+        self.top_k_percent_pixels = float(top_k_percent_pixels)
+        self.hard_example_mining_step = int(hard_example_mining_step)
+        self.__name__ = "sparse_crossentropy_top_k"
+
+    @property
+    def mining(self):
+        """(p, S) for the training engine; None where the object does not mine (p == 1)"""
+        return G.check_mining((self.top_k_percent_pixels, self.hard_example_mining_step))
+
+    def pixels_kept(self, step, n_pixels):
+        """k of the step that follows `step` completed optimizer updates, for a batch of n_pixels = B*H*W pixels: the
+        device's schedule (dl3_topk_threshold) restated on the host, every operation one rounded float32 operation —
+        pct = p if S == 0 else fl(fl(ratio*p) + fl(1 - ratio)), ratio = min(1, fl32(step)/fl32(S));
+        k = min(N, trunc(fl(pct * fl32(N))))"""
+        f = np.float32
+        p, S, N = f(self.top_k_percent_pixels), self.hard_example_mining_step, int(n_pixels)
+        pct = p
+        if S > 0:
+            ratio = min(f(1), f(f(int(step)) / f(S)))
+            pct = f(f(ratio * p) + f(f(1) - ratio))
+        return min(N, int(np.trunc(np.float64(f(pct * f(N))))))
+
+    def __call__(self, y_true, y_pred):
+        return sparse_crossentropy_ignoring_last_label(y_true, y_pred)
+
+    def __repr__(self):
+        return "sparse_crossentropy_top_k(%r, %r)" % (self.top_k_percent_pixels, self.hard_example_mining_step)
+
+
 def sparse_accuracy_ignoring_last_label(y_true, y_pred):
     """utils.py:132-138 on host."""
     C = y_pred.shape[-1]

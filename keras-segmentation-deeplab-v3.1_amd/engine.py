@@ -24,6 +24,7 @@ import torch
 from . import capi
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
 from .graph import check_mining, raw_pixels
+from .head import Head
 
 _ACT = {"relu": ACT_RELU, "relu6": ACT_RELU6}
 V_SCALE, V_SHIFT, V_MEAN, V_INVSTD, V_CA, V_CB, V_CC, V_NEGMEAN = range(8)
@@ -915,38 +916,29 @@ class Engine:
         if v.aff or v.act != ACT_NONE or v.off != 0 or v.ld != C:
             raise NotImplementedError("softmax expects materialised logits")
         self.logits_view = v
-        # training: fuse the final bilinear resize into the loss kernel (the full-resolution logits are interpolated in
-        # registers, never written): drop the resize launch from the forward plan, keep it for logits() on demand
-        self.fused_tail = None
+        # the head's form, decided here and nowhere else (head.py): the last launch only spreads materialised
+        # low-resolution logits (resize) / the Subpixel convolution's contiguous output (phase shift) into v
         last = self.units[-1] if self.units else None
-        if (self.training and isinstance(last, ResizeUnit) and last.outv.buf is v.buf and C <= 32
-                and not last.inv.aff and last.inv.act == ACT_NONE and last.inv.off == 0 and last.inv.ld == C):
-            self.fused_tail = last
-            self._resize_op = self.ops_fwd.pop()
-            assert self._resize_op[0] == "dl3_resize_bilinear_fwd"
-        # Subpixel head in training: the loss is evaluated straight on the unshuffled output of the Subpixel convolution
-        # (dl3_shuffle_softmax_xent): neither phase-shift pass nor the shuffled logits / gradient touch HBM; the forward
-        # phase shift is kept for logits() on demand
-        self.fused_shuffle = None
-        if (self.training and self.fused_tail is None and isinstance(last, ShuffleUnit) and last.outv.buf is v.buf
-                and os.environ.get("DL3_FUSE_SHUFFLE", "1") != "0"
-                # the fused kernel reads the Subpixel convolution's output as a plain contiguous tensor of co*r*r channels
-                # and writes that buffer's gradient itself: only with a single consumer and no view on top
-                and not last.inv.aff and last.inv.act == ACT_NONE and last.inv.off == 0
-                and last.inv.ld == last.co * last.r * last.r and last.inv.buf.expected == 1 and not last.inv.buf.bns
-                and self.lib.dl3_shuffle_xent_partials(self.B, last.inv.buf.H, last.inv.buf.W, last.co, last.r) > 0 and C <= 32):
-            self.fused_shuffle = last
-            self._shuffle_op = self.ops_fwd.pop()
-            assert self._shuffle_op[0] == "dl3_phase_shift"
+        form = "plain"
+        if (last is not None and last.outv.buf is v.buf and not last.inv.aff and last.inv.act == ACT_NONE
+                and last.inv.off == 0 and self.ops_fwd):
+            if isinstance(last, ResizeUnit) and last.inv.ld == C and self.ops_fwd[-1][0] == "dl3_resize_bilinear_fwd":
+                form = "bilinear"
+            elif (isinstance(last, ShuffleUnit) and last.inv.ld == last.co * last.r * last.r
+                  and self.ops_fwd[-1][0] == "dl3_phase_shift"):
+                form = "shuffle"
+        self.head = Head(self.B, v, form, last, self.ops_fwd[-1]) if form != "plain" else Head(self.B, v)
+        # training: what the loss (and the mining front) reads.  A fused form drops its launch from the forward plan — the
+        # full-resolution logits are never written; logits() runs it on demand
+        self.loss_head = self._loss_head() if self.training else None
+        if self.training and self.loss_head.op is not None:
+            self.ops_fwd.pop()
         M = v.buf.M
         self.probs = self.empty(M * C)
         self.out_shape = (self.B,) + tuple(l.output.shape)
         if self.training:
-            self.labels = self.zeros(M)
-            self.sweights = self.zeros(M)
+            self._alloc_targets()
             self.nnz = self.zeros(4)
-            self.lossP = self.lib.dl3_rows_partials(M)
-            self.loss_part = self.zeros(self.lossP)
             if self.external_nnz:
                 # data parallel: the loss kernel divides by a FIXED normaliser c0 (pixels per image: the same on every
                 # rank, whatever the shard), the shard's count(w != 0) and its loss sum land in the arena's tail, the ONE
@@ -959,6 +951,22 @@ class Engine:
                 self.loss = self.zeros(4)
             v.buf.expected += 1
         self.views[id(l.output)] = v
+
+    def _alloc_targets(self):
+        """labels / sample weights of the resident batch (set_targets)"""
+        M = self.logits_view.buf.M
+        self.labels, self.sweights = self.zeros(M), self.zeros(M)
+
+    def _loss_head(self):
+        """the training loss's admission rule: the fused kernels take at most 32 classes; the Subpixel one also reads its
+        source as a plain contiguous tensor and writes that buffer's gradient itself — only with a single consumer and no
+        BatchNorm on it, where its shape query accepts (DL3_FUSE_SHUFFLE=0: never)"""
+        h = self.head
+        ok = h.v.C <= 32
+        if ok and h.form == "shuffle":
+            ok = (os.environ.get("DL3_FUSE_SHUFFLE", "1") != "0" and h.src.buf.expected == 1 and not h.src.buf.bns
+                  and self.lib.dl3_shuffle_xent_partials(*h.dims("loss")) > 0)
+        return h if ok else h.plain
 
     # ------------------------------------------------------------------ backward lowering
     def _prune_gradients(self):
@@ -991,23 +999,13 @@ class Engine:
     def _lower_mining(self, M, C, count_dst):
         """the mining front of the loss kernel: v, (k, tau), (w', n').  -> the pointer the loss kernel takes as weights"""
         p, S = self.mining
-        v = self.logits_view
         self.mine_v, self.mine_w = self.empty(M), self.zeros(M)
         self.mine_tau = self.zeros(4)
         self.mine_k = torch.zeros(4, dtype=torch.int32, device=self.device)
         nws = int(self.lib.dl3_topk_workspace_bytes(M))
         self.mine_ws = torch.zeros(nws // 4, dtype=torch.int32, device=self.device)
-        self._mine_count = count_dst
-        args = (ptr(self.labels), ptr(self.sweights), ptr(self.mine_v))
-        if self.fused_shuffle is not None:
-            su = self.fused_shuffle
-            ub = su.inv.buf
-            self.op(self.ops_fwd, "dl3_pixel_xent_shuffle", su.inv.p(), *args, self.B, ub.H, ub.W, su.co, su.r)
-        elif self.fused_tail is not None:
-            lo = self.fused_tail.inv
-            self.op(self.ops_fwd, "dl3_pixel_xent_bilinear", lo.p(), *args, self.B, lo.buf.H, lo.buf.W, v.buf.H, v.buf.W, C)
-        else:
-            self.op(self.ops_fwd, "dl3_pixel_xent_plain", ptr(v.buf.t), *args, M, C)
+        self.op(self.ops_fwd, *self.loss_head.launch("pixel_xent", labels=ptr(self.labels), w=ptr(self.sweights),
+                                               out=ptr(self.mine_v)))
         self.op(self.ops_fwd, "dl3_topk_threshold", ptr(self.mine_v), M, p, S, self.mine_step.data_ptr(),
                 self.mine_ws.data_ptr(), nws, self.mine_k.data_ptr(), ptr(self.mine_tau))
         self.op(self.ops_fwd, "dl3_mine_weights", ptr(self.mine_v), ptr(self.sweights), ptr(self.mine_tau),
@@ -1038,34 +1036,22 @@ class Engine:
         else:
             self.op(self.ops_fwd, "dl3_count_nonzero", ptr(self.sweights), M, count_dst)
             wsrc = ptr(self.sweights)
-        if self.fused_shuffle is not None:
-            su = self.fused_shuffle
-            ub = su.inv.buf
-            ub.grad = self.empty(ub.M * ub.ld)
-            self.lossP = self.lib.dl3_shuffle_xent_partials(self.B, ub.H, ub.W, su.co, su.r)
-            self.loss_part = self.zeros(self.lossP)
-            self.op(self.ops_fwd, "dl3_shuffle_softmax_xent", su.inv.p(), ptr(self.labels), wsrc, ptr(self.nnz),
-                    ptr(ub.grad), ptr(self.loss_part), self.B, ub.H, ub.W, su.co, su.r)
-            su.fused = True
-        elif self.fused_tail is not None and ((buf.W + 2 * self.fused_tail.inv.buf.W) * C + 2 * buf.W) * 4 <= 65536 and self.fold_tail:
-            # the full-resolution gradient never exists: the loss kernel folds each output row onto the low-resolution
-            # columns, the resize unit's backward folds the rows
-            lo = self.fused_tail.inv
+        h = self.loss_head
+        # the full-resolution gradient never exists where a row of it fits the LDS: the loss kernel folds each output row
+        # onto the low-resolution columns, the resize unit's backward folds the rows
+        fold = h.form == "bilinear" and self.fold_tail and ((buf.W + 2 * h.src.buf.W) * C + 2 * buf.W) * 4 <= 65536
+        if h.form == "shuffle":     # the gradient of the Subpixel convolution's output, in its unshuffled layout
+            h.src.buf.grad = g = self.empty(h.src.buf.M * h.src.buf.ld)
+            self.lossP = self.lib.dl3_shuffle_xent_partials(*h.dims("loss"))
+        elif fold:
+            h.folded = g = self.empty(self.B * buf.H * h.src.buf.W * C)
             self.lossP = self.lib.dl3_xent_fold_partials(self.B, buf.H)
-            self.loss_part = self.zeros(self.lossP)
-            self.fused_tail.xfold = self.empty(self.B * buf.H * lo.buf.W * C)
-            self.op(self.ops_fwd, "dl3_upsample_softmax_xent_fold", lo.p(), ptr(self.labels), wsrc,
-                    ptr(self.nnz), ptr(self.fused_tail.xfold), ptr(self.loss_part), self.B, lo.buf.H, lo.buf.W, buf.H,
-                    buf.W, C)
-        elif self.fused_tail is not None:
-            buf.grad = self.empty(M * buf.ld)
-            lo = self.fused_tail.inv
-            self.op(self.ops_fwd, "dl3_upsample_softmax_xent", lo.p(), ptr(self.labels), wsrc,
-                    ptr(self.nnz), None, ptr(buf.grad), ptr(self.loss_part), self.B, lo.buf.H, lo.buf.W, buf.H, buf.W, C)
         else:
-            buf.grad = self.empty(M * buf.ld)
-            self.op(self.ops_fwd, "dl3_softmax_xent", ptr(buf.t), ptr(self.labels), wsrc, ptr(self.nnz),
-                    None, ptr(buf.grad), ptr(self.loss_part), M, C)
+            buf.grad = g = self.empty(M * buf.ld)
+            self.lossP = self.lib.dl3_rows_partials(M)
+        self.loss_part = self.zeros(self.lossP)
+        self.op(self.ops_fwd, *h.launch("loss", fold, labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz), grad=ptr(g),
+                                  part=ptr(self.loss_part)))
         self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP, 1, ptr(self.loss))
         buf.done = 1
         assert buf.expected == 1
@@ -1187,21 +1173,13 @@ class Engine:
 
     def contrib_elementwise(self, buf, view, gin, ldgin, gin_div=1, gin_scale=1.0, drop=(0.0, 0)):
         """contribution through dl3_grad_finish: gout = mask_view(gin) + existing; handles stats when last"""
-        gout, add, last = self.contrib_kernel(buf)
-        need_stat = last and bool(buf.bns)
-        P = self.lib.dl3_rows_partials(buf.M)
-        dpart = self.empty(P * buf.ld * 2) if need_stat else None
-        masked = view.act != ACT_NONE
-        need_x = masked or need_stat
         if view.off != 0 or view.C != buf.ld:
             raise NotImplementedError("element-wise gradient into a channel slice")
-        self.op(self.ops_bwd, "dl3_grad_finish", gin, ldgin, gin_div, gin_scale, ptr(gout), buf.ld,
-                ptr(add), buf.ld, ptr(buf.t) if need_x else None, buf.ld,
-                view.scale() if masked else None, view.shift() if masked else None, view.act,
-                buf.vptr(V_MEAN) if need_stat else None, buf.vptr(V_INVSTD) if need_stat else None, ptr(dpart),
-                buf.M, buf.ld, drop[0], drop[1], self.drop_step.data_ptr() if drop[0] > 0 else None)
-        if need_stat:
-            self.finish_bn_bwd(buf, dpart, P, buf.ld)
+        k = GradSink(self, view, self.lib.dl3_rows_partials(buf.M))
+        self.op(self.ops_bwd, "dl3_grad_finish", gin, ldgin, gin_div, gin_scale, k.out, buf.ld, k.add, buf.ld, k.x, buf.ld,
+                k.scale, k.shift, view.act, k.mean, k.invstd, ptr(k.dpart), buf.M, buf.ld, drop[0], drop[1],
+                self.drop_step.data_ptr() if drop[0] > 0 else None)
+        k.finish()
 
     def contrib_passthrough(self, buf, view, g):
         """Add backward: the gradient tensor g (same [M, C] shape, ld == C) flows unchanged into buf"""
@@ -1300,10 +1278,8 @@ class Engine:
 
     def logits(self):
         v = self.logits_view
-        if getattr(self, "fused_tail", None) is not None:
-            self.run_ops([self._resize_op])  # the fused training tail never materialises them
-        if getattr(self, "fused_shuffle", None) is not None:
-            self.run_ops([self._shuffle_op])  # nor does the fused Subpixel tail
+        if self.training and self.loss_head.op is not None:
+            self.run_ops([self.loss_head.op])  # a fused training tail never materialises them
         return v.buf.t.cpu().numpy().reshape(self.B, v.buf.H, v.buf.W, v.C)
 
     def argmax(self, host=True):
@@ -1385,53 +1361,29 @@ class Engine:
             raise RuntimeError("Engine.evaluate_batch needs an inference engine (training=False)")
         M, C, B = self.logits_view.buf.M, self.logits_view.C, self.B
 
-        def partials(form, dims):
-            return getattr(self.lib, "dl3_eval_tail_%s_partials" % form)(*dims)
-        # the fused kernel's own limits (C <= 32, LDS staging): its *_partials query answers 0 for a shape it refuses
-        form, src, dims, ops = self._fused_head(partials)
-        P = partials(form, dims)
+        def partials(h):
+            return getattr(self.lib, h.entry("eval_tail")[0] + "_partials")(*h.dims("eval_tail"))
+        # the evaluation tail's admission rule: the fused kernel's own limits (C <= 32, LDS staging) — its *_partials
+        # query answers 0 for a shape it refuses
+        h = self.head if partials(self.head) > 0 else self.head.plain
+        P = partials(h)
         if P <= 0:
             raise capi.DL3Error("dl3_eval_tail_plain does not support %d classes" % C)
         # labels / weights of the batch (set_targets), the tail's own buffers and ONE record of its results:
         # loss_sum double[B] | nnz int32[B] | counts int32[B][3][C]
-        self.labels = self.zeros(M)
-        self.sweights = self.zeros(M)
+        self._alloc_targets()
         rec_bytes = (8 * B + 4 * B + 4 * B * 3 * C + 15) // 16 * 16
         self._eval = ev = types.SimpleNamespace(
-            form=form, src=src, dims=dims, ops=ops, plans={}, n=0, rec_bytes=rec_bytes, part=self.empty(2 * B * P),
+            head=h, plans={}, n=0, rec_bytes=rec_bytes, part=self.empty(2 * B * P),
             mask=torch.empty(M, dtype=torch.int32, device=self.device),
             rec=torch.zeros(rec_bytes, dtype=torch.uint8, device=self.device),
             results=torch.zeros(8, rec_bytes, dtype=torch.uint8, device=self.device))
         return ev
 
-    def _fused_head(self, accepts=None):
-        """what the evaluation plan and the CRF-unary plan share: (form, source pointer, dims) of _tail_source() and the
-        forward op list, without its last launch where a fused form reads in front of that launch.  accepts(form, dims):
-        the fused kernel's own shape query; an answer <= 0 falls back to the plain form, and nothing is dropped."""
-        form, src, dims = self._tail_source()
-        if form != "plain" and accepts is not None and accepts(form, dims) <= 0:
-            v = self.logits_view
-            form, src, dims = "plain", ptr(v.buf.t), (self.B, v.buf.M // self.B, v.C)
-        return form, src, dims, (self.ops_fwd[:-1] if form != "plain" else list(self.ops_fwd))
-
-    def _tail_source(self):
-        """what a fused tail (evaluation, CRF unary) may read instead of the full-resolution logits: ("bilinear", pointer,
-        (B, Hi, Wi, Ho, Wo, C)) when the forward plan ends in dl3_resize_bilinear_fwd over materialised low-resolution
-        logits, ("shuffle", pointer, (B, H, W, C, r)) when it ends in dl3_phase_shift over the Subpixel convolution's
-        output — the tail then runs the plan without that last launch —, else ("plain", the head's logits, (B, HW, C))"""
-        v = self.logits_view
-        C, B = v.C, self.B
-        ops = self.ops_fwd
-        last = self.units[-1] if self.units else None
-        if last is not None and last.outv.buf is v.buf and ops and not last.inv.aff and last.inv.act == ACT_NONE \
-                and last.inv.off == 0:
-            if isinstance(last, ResizeUnit) and ops[-1][0] == "dl3_resize_bilinear_fwd" and last.inv.ld == C:
-                _, Hi, Wi, Ho, Wo, _ = last.dims
-                return "bilinear", last.inv.p(), (B, Hi, Wi, Ho, Wo, C)
-            if isinstance(last, ShuffleUnit) and ops[-1][0] == "dl3_phase_shift" \
-                    and last.inv.ld == last.co * last.r * last.r and last.co == C:
-                return "shuffle", last.inv.p(), (B, last.inv.buf.H, last.inv.buf.W, C, last.r)
-        return "plain", ptr(v.buf.t), (B, v.buf.M // B, C)
+    def _ops_before(self, h):
+        """the forward op list in front of a kernel that reads head h: without the launch that materialises the
+        full-resolution logits where h is a fused form (`ops_fwd` itself stays as it is)"""
+        return self.ops_fwd[:-1] if h.op is not None else list(self.ops_fwd)
 
     def eval_op_names(self, confusion=None, mask=False):
         """the launch names of the evaluation plan (tests: no final resize / phase shift / softmax in it)"""
@@ -1447,11 +1399,11 @@ class Engine:
                                           or not confusion.is_contiguous() or confusion.device != self.device):
                 raise ValueError("confusion must be a contiguous int64 [%d,%d] tensor on %s" % (C, C, self.device))
             base = ev.rec.data_ptr()
-            args = [ev.src, ptr(self.labels), ptr(self.sweights) if weighted else None, ptr(ev.part), base,
-                    base + 8 * B, base + 12 * B, None if confusion is None else confusion.data_ptr(),
-                    ev.mask.data_ptr() if mask else None] + list(ev.dims)
-            name = "dl3_eval_tail_" + ev.form
-            ops = ev.ops + [(name, getattr(self.lib, name), args, None)]
+            ops = self._ops_before(ev.head)
+            self.op(ops, *ev.head.launch(
+                "eval_tail", labels=ptr(self.labels), w=ptr(self.sweights) if weighted else None, part=ptr(ev.part),
+                loss=base, nnz=base + 8 * B, counts=base + 12 * B, confusion=None if confusion is None else confusion.data_ptr(),
+                mask=ev.mask.data_ptr() if mask else None))
             # (confusion rides along so that the tensor behind the captured pointer stays alive)
             ev.plans[key] = (Plan(self, lambda: self.run_ops(ops)), ops, confusion)
         return ev.plans[key][:2]
@@ -1500,29 +1452,26 @@ class Engine:
         return loss, nnz, counts
 
     # ------------------------------------------------------------------ CRF unary plan (softmax unary)
-    def _crf_setup(self):
+    def _crf_ops(self, U_ptr, scale, clip, form=None):
         """the plan behind crf_unary: like the evaluation plan, the forward op list minus the final resize / phase-shift
-        launch where that launch only spreads materialised low-resolution logits (`ops_fwd` itself stays as it is), ending
-        in dl3_crf_unary_bilinear / _shuffle on those; any other graph keeps its whole forward plan and ends in
-        dl3_crf_unary_plain on the head's logits.  No softmax launch either way.  -> (form, source, dims, forward ops)"""
-        if getattr(self, "_crf", None) is None:
-            if self.training:
-                raise RuntimeError("Engine.crf_unary needs an inference engine (training=False)")
-            self._crf = self._fused_head()
-        return self._crf
+        launch where that launch only spreads materialised low-resolution logits, ending in dl3_crf_unary_bilinear /
+        _shuffle on those; any other graph — or form="plain" — keeps its whole forward plan and ends in dl3_crf_unary_plain
+        on the head's logits.  No softmax launch either way, and no admission rule: the kernels take every shape."""
+        if self.training:
+            raise RuntimeError("Engine.crf_unary needs an inference engine (training=False)")
+        if form not in (None, "plain", self.head.form):
+            raise ValueError("this head has no %r form (it is %r)" % (form, self.head.form))
+        h = self.head.plain if form == "plain" else self.head
+        ops = self._ops_before(h)
+        self.op(ops, *h.launch("crf_unary", U=U_ptr, scale=0.0 if scale is None else float(scale),
+                               clip=0.0 if clip is None else float(clip)))
+        return ops
 
-    def _crf_ops(self, U_ptr, scale, clip):
-        form, src, dims, ops = self._crf_setup()
-        sc, cl = (0.0 if scale is None else float(scale)), (0.0 if clip is None else float(clip))
-        name = "dl3_crf_unary_" + form
-        args = ([src, 0, U_ptr] if form == "plain" else [src, U_ptr]) + list(dims) + [sc, cl]
-        return ops + [(name, getattr(self.lib, name), args, None)]
-
-    def crf_unary_op_names(self):
+    def crf_unary_op_names(self, form=None):
         """the launch names of the CRF unary plan (tests: which form, and no final resize / phase shift / softmax)"""
-        return [rec[0] for rec in self._crf_ops(None, None, 1e-5)]
+        return [rec[0] for rec in self._crf_ops(None, None, 1e-5, form)]
 
-    def crf_unary(self, U=None, scale=None, clip=1e-5):
+    def crf_unary(self, U=None, scale=None, clip=1e-5, form=None):
         """forward pass on the resident input (set_input) straight into the dense CRF's unary energies: U [B,C,N] float32
         on the device (allocated when not given), unary_from_softmax(softmax(logits), scale, clip) of the full-resolution
         logits — which, like the probabilities, are not written where the head ends in a resize or a phase shift."""
@@ -1533,7 +1482,7 @@ class Engine:
               or not U.is_contiguous() or U.device != self.device):
             raise ValueError("U must be a contiguous float32 [%d,%d,%d] tensor on %s" % (self.B, C, N, self.device))
         self._prep()
-        self.run_ops(self._crf_ops(U.data_ptr(), scale, clip))
+        self.run_ops(self._crf_ops(U.data_ptr(), scale, clip, form))
         return U
 
     def crf_mask(self, images, scale=None, clip=1e-5):
@@ -1678,6 +1627,47 @@ class Engine:
         kind, off, n, shp, _ = self.slots[name]
         assert kind == "p"
         return self._unpad(name, self.grads[off:off + n].cpu().numpy().reshape(shp))
+
+
+class GradSink:
+    """A kernel is about to write the data gradient of view `inv`, and its epilogue can reduce P partial rows: the one
+    place that knows what it needs to be told about that buffer (the six bwd-data sites take their arguments from here).
+    out / add: output and addend pointers at the view's channel offset; scale / shift: the mask's, where the view has an
+    activation; x: the forward input, where the mask or the sums need it; sx / sld / mean / invstd / dpart: what the
+    BatchNorm-backward sums ride along on — against the input's own BatchNorm when this contribution is the last, or
+    (alias=True: the caller's epilogue can) against the BatchNorm the gradient reaches unchanged through the residual
+    Add whose output this is (Engine.alias_stats_target, .tgt); finish(): fold the sums, or park them for that Add."""
+    out = add = x = scale = shift = sx = mean = invstd = dpart = tgt = None
+    sld, stat = 0, False
+
+    def __init__(self, eng, inv, P, alias=False):
+        self.eng, self.buf, self.P = eng, inv.buf, P
+        buf, off = inv.buf, inv.off
+        if not buf.requires_grad:   # nothing to write (a kernel that computes another gradient in the same launch)
+            return
+        gout, add, last = eng.contrib_kernel(buf)
+        whole = off == 0 and inv.C == buf.ld
+        self.stat = last and bool(buf.bns)
+        if self.stat and not whole:
+            raise NotImplementedError("BN-backward statistics through a channel slice")
+        self.out = gout.data_ptr() + 4 * off
+        self.add = None if add is None else add.data_ptr() + 4 * off
+        if inv.act != ACT_NONE:
+            self.scale, self.shift = inv.scale(), inv.shift()
+        if inv.act != ACT_NONE or self.stat:
+            self.x = inv.p()
+        if alias and last and not self.stat and whole:
+            self.tgt = eng.alias_stats_target(buf)
+        sbuf = self.tgt if self.tgt is not None else (buf if self.stat else None)
+        if sbuf is not None:   # (a whole view either way: every offset is 0)
+            self.sx, self.sld, self.mean, self.invstd = ptr(sbuf.t), sbuf.ld, sbuf.vptr(V_MEAN), sbuf.vptr(V_INVSTD)
+            self.dpart = eng.empty(P * sbuf.ld * 2)
+
+    def finish(self):
+        if self.tgt is not None:
+            self.eng.prestat[id(self.tgt)] = (self.dpart, self.P, self.tgt.ld)
+        elif self.stat:
+            self.eng.finish_bn_bwd(self.buf, self.dpart, self.P, self.buf.ld)
 
 
 class LazyLoss:
@@ -1830,33 +1820,18 @@ class PwUnit(_ConvBase):
         ibuf = inv.buf
         wT = eng.empty(K * N)
         eng.transpose(eng.wptr(self.wname()), wT, K, N)
-        gout, add, last = eng.contrib_kernel(ibuf)
-        need_stat = last and bool(ibuf.bns)
-        if need_stat and (inv.off != 0 or inv.C != ibuf.ld):
-            raise NotImplementedError("BN-backward statistics through a channel slice")
         S = eng.lib.dl3_pwconv_bwd_fused_splits(M, K, N)
         ws = eng.lib.dl3_pwconv_bwd_fused_workspace(M, K, N)
-        tgt = None
-        if last and not need_stat and a == ACT_NONE and inv.off == 0 and inv.C == ibuf.ld:
-            tgt = eng.alias_stats_target(ibuf)   # see bwd(): the sums of the BatchNorm the gradient reaches through the Add
-        sbuf = tgt if tgt is not None else (ibuf if need_stat else None)
-        dpart = eng.empty(S * sbuf.ld * 2) if sbuf is not None else None
+        k = GradSink(eng, inv, S, alias=a == ACT_NONE)
         own = eng.empty(ws // 4 + 4)
         eng.own_fold_ws_bytes += ws + 16
         eng.op(eng.ops_bwd, "dl3_pwconv_bwd_fused", inv.p(), inv.ld, s, t, a, g, ldg, y, ldy, cA, cB, cC, ptr(wT), None,
-               gout.data_ptr() + 4 * inv.off, ibuf.ld, (add.data_ptr() + 4 * inv.off) if add is not None else None, ibuf.ld,
-               (sbuf.t.data_ptr() + (4 * inv.off if sbuf is ibuf else 0)) if sbuf is not None else None,
-               sbuf.ld if sbuf is not None else 0, sbuf.vptr(V_MEAN, inv.off if sbuf is ibuf else 0) if sbuf is not None else None,
-               sbuf.vptr(V_INVSTD, inv.off if sbuf is ibuf else 0) if sbuf is not None else None, ptr(dpart), M, K, N,
-               ptr(own), ws)
+               k.out, ibuf.ld, k.add, ibuf.ld, k.sx, k.sld, k.mean, k.invstd, ptr(k.dpart), M, K, N, ptr(own), ws)
         if eng.defer_fold(S, K * N):
             eng.fold(ptr(own), S, K * N, eng.gptr(self.wname()))
         else:
             eng.op(eng.ops_bwd, "dl3_reduce_partials", ptr(own), S, K * N, eng.gptr(self.wname()))
-        if tgt is not None:
-            eng.prestat[id(tgt)] = (dpart, S, tgt.ld)
-        elif need_stat:
-            eng.finish_bn_bwd(ibuf, dpart, S, ibuf.ld)
+        k.finish()
 
     def bwd(self):
         if self.fused_ok():
@@ -1892,33 +1867,12 @@ class PwUnit(_ConvBase):
             return
         wT = eng.empty(K * N)
         eng.transpose(wsrc, wT, K, N)
-        gout, add, last = eng.contrib_kernel(ibuf)
-        need_stat = last and bool(ibuf.bns)
-        P = eng.lib.dl3_pwconv_partials(M, N, K)
-        dpart = eng.empty(P * ibuf.ld * 2) if need_stat else None
-        if need_stat and (inv.off != 0 or inv.C != ibuf.ld):
-            raise NotImplementedError("BN-backward statistics through a channel slice")
-        need_x = a != ACT_NONE or need_stat
-        tgt = None
-        if last and not need_x and inv.off == 0 and inv.C == ibuf.ld:
-            # the epilogue's forward-input slot is free (no mask, no BatchNorm on the Add output): use it for the sums of
-            # the BatchNorm this gradient reaches unchanged through the residual Add
-            tgt = eng.alias_stats_target(ibuf)
-        if tgt is not None:
-            dpart = eng.empty(P * tgt.ld * 2)
-            eng.op(eng.ops_bwd, "dl3_pwconv_bwd_data", g, ldg, y, ldy, cA, cB, cC, ptr(wT), ptr(gout), ibuf.ld,
-                   ptr(tgt.t), tgt.ld, None, None, ACT_NONE, ptr(add), ibuf.ld, 1, 1.0,
-                   tgt.vptr(V_MEAN), tgt.vptr(V_INVSTD), ptr(dpart), M, K, N)
-            eng.prestat[id(tgt)] = (dpart, P, tgt.ld)
-            return
-        eng.op(eng.ops_bwd, "dl3_pwconv_bwd_data", g, ldg, y, ldy, cA, cB, cC, ptr(wT),
-               gout.data_ptr() + 4 * inv.off, ibuf.ld, inv.p() if need_x else None, inv.ld,
-               s if a != ACT_NONE else None, t if a != ACT_NONE else None, a,
-               (add.data_ptr() + 4 * inv.off) if add is not None else None, ibuf.ld, 1, 1.0,
-               ibuf.vptr(V_MEAN, inv.off) if need_stat else None, ibuf.vptr(V_INVSTD, inv.off) if need_stat else None,
-               ptr(dpart), M, K, N)
-        if need_stat:
-            eng.finish_bn_bwd(ibuf, dpart, P, ibuf.ld)
+        # alias: with no mask and no BatchNorm on a residual Add's output the epilogue's forward-input slot is free — it
+        # takes the sums of the BatchNorm this gradient reaches unchanged through the Add
+        k = GradSink(eng, inv, eng.lib.dl3_pwconv_partials(M, N, K), alias=a == ACT_NONE)
+        eng.op(eng.ops_bwd, "dl3_pwconv_bwd_data", g, ldg, y, ldy, cA, cB, cC, ptr(wT), k.out, ibuf.ld, k.x or k.sx, inv.ld,
+               k.scale, k.shift, a, k.add, ibuf.ld, 1, 1.0, k.mean, k.invstd, ptr(k.dpart), M, K, N)
+        k.finish()
 
 
 class DwUnit(_ConvBase):
@@ -1945,35 +1899,21 @@ class DwUnit(_ConvBase):
         g, ldg, y, ldy, cA, cB, cC = eng.grad_operand(outv)
         assert ldg == C
         s, t, a = inv.xform()
-        ibuf = inv.buf
         wpart = eng.empty(self.P * 9 * C)
-        gout = add = dpart = None
-        need_stat = False
-        tgt = None
-        if ibuf.requires_grad:
-            gout, add, last = eng.contrib_kernel(ibuf)
-            need_stat = last and bool(ibuf.bns)
-            dpart = eng.empty(self.P * C * 2) if need_stat else None
-            B_, H, W, _, stride, rate, pt, pl, Ho, Wo = self.geom
-            if (last and not ibuf.bns and stride == 1 and Ho == H and Wo == W and pt == rate and pl == rate
-                    and eng.dw_impl in (IMPL_AUTO, capi.IMPL_MARCH)):
-                # this launch completes the gradient of a residual Add's output (Xception's `sum` shortcuts): the sums of the
-                # BatchNorm it reaches unchanged through the Add ride along (round 4; PwUnit.bwd does the same for
-                # MobileNetV2's blocks) instead of a dl3_grad_finish pass over g and y
-                tgt = eng.alias_stats_target(ibuf)
-        if tgt is not None:
-            dpart = eng.empty(self.P * C * 2)
+        B_, H, W, _, stride, rate, pt, pl, Ho, Wo = self.geom
+        # alias: a launch that completes the gradient of a residual Add's output (Xception's `sum` shortcuts) takes the sums
+        # of the BatchNorm it reaches unchanged through the Add along (round 4; PwUnit.bwd does the same for MobileNetV2's
+        # blocks) instead of a dl3_grad_finish pass over g and y
+        k = GradSink(eng, inv, self.P, alias=(stride == 1 and Ho == H and Wo == W and pt == rate and pl == rate
+                                              and eng.dw_impl in (IMPL_AUTO, capi.IMPL_MARCH)))
+        if k.tgt is not None:
             eng.op(eng.ops_bwd, "dl3_dwconv3x3_bwd_sx", g, y, cA, cB, cC, inv.p(), s, t, a, eng.wptr(self.wname()),
-                   ptr(gout), ptr(add), ptr(tgt.t), tgt.vptr(V_MEAN), tgt.vptr(V_INVSTD), ptr(dpart), ptr(wpart),
-                   *self.geom, eng.dw_impl)
-            eng.prestat[id(tgt)] = (dpart, self.P, C)
+                   k.out, k.add, k.sx, k.mean, k.invstd, ptr(k.dpart), ptr(wpart), *self.geom, eng.dw_impl)
         else:
             eng.op(eng.ops_bwd, "dl3_dwconv3x3_bwd", g, y, cA, cB, cC, inv.p(), s, t, a, eng.wptr(self.wname()),
-                   ptr(gout), ptr(add), ibuf.vptr(V_MEAN) if need_stat else None,
-                   ibuf.vptr(V_INVSTD) if need_stat else None, ptr(dpart), ptr(wpart), *self.geom, eng.dw_impl)
+                   k.out, k.add, k.mean, k.invstd, ptr(k.dpart), ptr(wpart), *self.geom, eng.dw_impl)
         eng.fold(ptr(wpart), self.P, 9 * C, eng.gptr(self.wname()))
-        if need_stat:
-            eng.finish_bn_bwd(ibuf, dpart, self.P, C)
+        k.finish()
 
 
 class Conv3Unit(_ConvBase):
@@ -2019,17 +1959,10 @@ class Conv3Unit(_ConvBase):
             return
         wT = eng.empty(9 * Cin * Cout)
         eng.transpose(eng.wptr(self.wname()), wT, 9 * Cin, Cout)
-        gout, add, last = eng.contrib_kernel(ibuf)
-        need_stat = last and bool(ibuf.bns)
-        P = eng.lib.dl3_conv3x3_mfma_partials(B, H, W)
-        dpart = eng.empty(P * Cin * 2) if need_stat else None
-        need_x = a != ACT_NONE or need_stat
-        eng.op(eng.ops_bwd, "dl3_conv3x3_mfma_bwd_data", g, y, cA, cB, cC, ptr(wT), ptr(gout),
-               inv.p() if need_x else None, s if a != ACT_NONE else None, t if a != ACT_NONE else None, a, ptr(add),
-               ibuf.vptr(V_MEAN) if need_stat else None, ibuf.vptr(V_INVSTD) if need_stat else None, ptr(dpart),
-               *self.geom)
-        if need_stat:
-            eng.finish_bn_bwd(ibuf, dpart, P, Cin)
+        k = GradSink(eng, inv, eng.lib.dl3_conv3x3_mfma_partials(B, H, W))
+        eng.op(eng.ops_bwd, "dl3_conv3x3_mfma_bwd_data", g, y, cA, cB, cC, ptr(wT), k.out, k.x, k.scale, k.shift, a, k.add,
+               k.mean, k.invstd, ptr(k.dpart), *self.geom)
+        k.finish()
 
     def bwd(self):
         if self.gemm:
@@ -2045,17 +1978,10 @@ class Conv3Unit(_ConvBase):
         ibuf = inv.buf
         if not ibuf.requires_grad:
             return
-        gout, add, last = eng.contrib_kernel(ibuf)
-        need_stat = last and bool(ibuf.bns)
-        P = eng.lib.dl3_conv3x3_partials(B, H, W, Cin)
-        dpart = eng.empty(P * Cin * 2) if need_stat else None
-        need_x = a != ACT_NONE or need_stat
-        eng.op(eng.ops_bwd, "dl3_conv3x3_bwd_data", g, y, cA, cB, cC, eng.wptr(self.wname()), ptr(gout),
-               inv.p() if need_x else None, s if a != ACT_NONE else None, t if a != ACT_NONE else None, a, ptr(add),
-               ibuf.vptr(V_MEAN) if need_stat else None, ibuf.vptr(V_INVSTD) if need_stat else None, ptr(dpart),
-               *self.geom)
-        if need_stat:
-            eng.finish_bn_bwd(ibuf, dpart, P, Cin)
+        k = GradSink(eng, inv, eng.lib.dl3_conv3x3_partials(B, H, W, Cin))
+        eng.op(eng.ops_bwd, "dl3_conv3x3_bwd_data", g, y, cA, cB, cC, eng.wptr(self.wname()), k.out, k.x, k.scale, k.shift, a,
+               k.add, k.mean, k.invstd, ptr(k.dpart), *self.geom)
+        k.finish()
 
 
 class AddUnit:
@@ -2125,11 +2051,10 @@ class ResizeUnit:
         if not ibuf.requires_grad:
             return
         B, Hi, Wi, Ho, Wo, C = self.dims
-        xfold = getattr(self, "xfold", None)
-        if xfold is not None:
+        if eng.loss_head.unit is self and eng.loss_head.folded is not None:
             # fused training tail: the loss kernel already folded the output columns (dl3_upsample_softmax_xent_fold)
             gout, add, last = eng.contrib_kernel(ibuf)
-            eng.op(eng.ops_bwd, "dl3_resize_bilinear_bwd_rows", ptr(xfold), ptr(gout), ibuf.ld, B, Hi, Wi, Ho, C,
+            eng.op(eng.ops_bwd, "dl3_resize_bilinear_bwd_rows", ptr(eng.loss_head.folded), ptr(gout), ibuf.ld, B, Hi, Wi, Ho, C,
                    1 if add is not None else 0)
             if add is not None and add is not gout:
                 raise NotImplementedError("resize backward with a foreign addend")
@@ -2164,11 +2089,9 @@ class ShuffleUnit:
         eng._consume(inv)
         eng.op(eng.ops_fwd, "dl3_phase_shift", inv.p(), outv.p(), eng.B, inv.buf.H, inv.buf.W, co, r, 0)
 
-    fused = False  # training: the loss kernel wrote the gradient in the unshuffled layout already (Engine._lo_softmax)
-
     def bwd(self):
         eng, inv = self.eng, self.inv
-        if self.fused:
+        if eng.loss_head.unit is self:   # the loss kernel wrote the gradient in the unshuffled layout already
             assert inv.buf.grad is not None and not inv.buf.bns
             inv.buf.done += 1
             return

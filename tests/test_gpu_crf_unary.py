@@ -326,16 +326,11 @@ def test_predict_mask_softmax_unary(backbone, head, op, gone):
     assert torch.equal(Uplan.view(torch.int32), Uplain.view(torch.int32))
     # the engine's plain route (a head that ends in neither a resize nor a phase shift), forced on this model: the whole
     # forward plan, then dl3_crf_unary_plain on the head's logits, and the same U
-    eng._crf, eng._tail_source = None, lambda: ("plain", eng.logits_view.buf.t.data_ptr(), (B, 64 * 64, C))
-    try:
-        names = eng.crf_unary_op_names()
-        assert names[-1] == "dl3_crf_unary_plain" and names[:-1] == fwd
-        Uforced = eng.crf_unary()
-        torch.cuda.synchronize()
-        assert torch.equal(Uforced.view(torch.int32), Uplan.view(torch.int32))
-    finally:
-        del eng._tail_source
-        eng._crf = None
+    names = eng.crf_unary_op_names(form="plain")
+    assert names[-1] == "dl3_crf_unary_plain" and names[:-1] == fwd
+    Uforced = eng.crf_unary(form="plain")
+    torch.cuda.synchronize()
+    assert torch.equal(Uforced.view(torch.int32), Uplan.view(torch.int32))
     assert eng.crf_unary_op_names()[-1] == op
     print("%s/%s: %s, %d of %d pixels differ from the arg-max mask" % (backbone, head, op, int((got != plain0).sum()), got.size))
     assert np.array_equal(got, want)

@@ -272,10 +272,10 @@ def _drop_engines(model):
 
 
 def _lowres_logits(eng):
-    ft = getattr(eng, "fused_tail", None)
-    if ft is not None:
-        b = ft.inv.buf
-        return b.t.view(b.M, b.ld)[:, ft.inv.off:ft.inv.off + ft.inv.C].double()
+    h = eng.loss_head
+    if h is not None and h.form == "bilinear":   # the fused training tail: the view its loss kernel reads
+        b, src = h.src.buf, h.src
+        return b.t.view(b.M, b.ld)[:, src.off:src.off + src.C].double()
     return torch.from_numpy(eng.logits()).double().cuda().reshape(-1, eng.logits_view.C)
 
 

@@ -1021,7 +1021,7 @@ def test_subpixel_head_fused_loss_equals_unfused(monkeypatch):
     for fuse in ("1", "0"):
         monkeypatch.setenv("DL3_FUSE_SHUFFLE", fuse)
         eng = model._engine(2, True, dropout=False, use_graph=False, seed=300 + int(fuse))
-        assert (eng.fused_shuffle is not None) == (fuse == "1")
+        assert eng.head.form == "shuffle" and eng.loss_head.form == ("shuffle" if fuse == "1" else "plain")
         names = [o[0] for o in eng.ops_fwd + eng.ops_bwd]
         assert ("dl3_phase_shift" in names) == (fuse == "0") and ("dl3_shuffle_softmax_xent" in names) == (fuse == "1")
         eng.set_input(x)

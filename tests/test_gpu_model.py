@@ -642,10 +642,27 @@ def test_width_multiplier_alpha():
     params = O.calibrate_bn(params, x, **kw)
     _load(model, params)
     assert model.get_layer("expanded_conv_project").get_weights()[0].shape[-1] == 8
-    ref, _ = O.forward({k: v.astype(np.float64) for k, v in params.items()}, x.astype(np.float64), **kw)
+    p64 = {k: v.astype(np.float64) for k, v in params.items()}
+    ref, _ = O.forward(p64, x.astype(np.float64), **kw)
     model.predict(x, batch_size=B)
     assert relerr(model._active.logits(), ref) < 1e-3
     _assert_argmax_parity(model._active.argmax(), ref)
+    # one training step's gradients (the 16-channel stem runs the direct 3x3 kernels at CQ = 4, PL = 64): the bars of
+    # test_odd_and_non_square_inputs
+    labels = rng.integers(0, classes + 1, (B, shape[0] * shape[1])).astype(np.float32)
+    sw = (labels < classes).astype(np.float32)
+    eng = model._engine(B, True, dropout=False, use_graph=False)
+    eng.set_input(x)
+    eng.set_targets(labels, sw)
+    eng.fwd_bwd()
+    torch.cuda.synchronize()
+    loss, grads, logits, _ = O.train_grads(p64, x.astype(np.float64), labels.astype(np.float64), sw.astype(np.float64), **kw)
+    assert relerr(eng.logits(), logits) < 1e-3
+    assert abs(float(eng.loss[0].item()) - loss) < 1e-4 * abs(loss)
+    name = "custom_logits_semantic/kernel:0"
+    d = _l2(eng.grad_of(name), grads[name])
+    print("   %-36s gradient rel-L2 gpu %.2e" % (name, d))
+    assert d < 1e-3, (name, d)
     y = rng.integers(0, classes + 1, (B, shape[0] * shape[1], 1)).astype(np.float32)
     l0 = model.train_on_batch(x, y)
     assert np.isfinite(l0)

@@ -61,7 +61,10 @@ const char *dl3_last_error(void);
 
 /* ---- DepthwiseConv2D 3x3 (deeplabv3p.py:73-74, :186-188) ------------------------------ */
 /* number of partial rows P written by dwconv fwd (stat_partial [P][C][2]) and bwd
- * (dstat_partial [P][C][2], dw_partial [P][9][C]) for this shape/impl */
+ * (dstat_partial [P][C][2], dw_partial [P][9][C]) for this shape/impl.  The pads are not an argument: DL3_IMPL_AUTO counts
+ * the rows of the march kernels for every stride-1 geometry with Ho == H and Wo == W.  Where such a geometry's pads are not
+ * its rate the launches need the gather kernels and more rows: they return DL3_EUNSUPPORTED under DL3_IMPL_AUTO; size and
+ * launch it with DL3_IMPL_GATHER. */
 int dl3_dwconv3x3_partials(int N, int H, int W, int C, int stride, int rate, int Ho, int Wo, int impl);
 /* y[n,oy,ox,c] = sum_{i,j} T(x)[n, oy*stride-pad_t+i*rate, ox*stride-pad_l+j*rate, c] * w[i][j][c];
  * stat_partial (nullable): per-channel sum(y), sum(y^2) partials */

@@ -951,13 +951,27 @@ int resolve_impl(int impl, int H, int W, int stride, int rate, int pad_t, int pa
   return impl;
 }
 
+// what dl3_dwconv3x3_partials(DL3_IMPL_AUTO), which is not told the pads, takes for a march geometry
+bool auto_sized_for_march(int H, int W, int stride, int Ho, int Wo) {
+  return stride == 1 && Ho == H && Wo == W;
+}
+
+// DL3_IMPL_AUTO on a stride-1, Ho == H, Wo == W geometry whose pads are not the rate: the caller's partial buffers hold the
+// march row count, the launch would run the gather kernels and write gridDim.y rows (1 x 16 x 16 x 32 at rate 1 with
+// pad_t = 0: 2 rows allocated, 8 written, of [C][2] and of [9][C] floats)
+bool auto_mismatch(int impl, int im, int H, int W, int stride, int Ho, int Wo) {
+  return impl == DL3_IMPL_AUTO && im == DL3_IMPL_GATHER && auto_sized_for_march(H, W, stride, Ho, Wo);
+}
+
 }  // namespace
 
 extern "C" int dl3_dwconv3x3_partials(int N, int H, int W, int C, int stride, int rate, int Ho, int Wo,
                                       int impl) {
-  // pads are implied: march needs SAME stride-1 geometry, which the caller guarantees when it asks for it
+  // The pads are not an argument.  DL3_IMPL_AUTO counts march rows for every stride-1 geometry with Ho == H and Wo == W;
+  // the launchers take the march kernels only where the pads equal the rate as well (march_ok) and refuse DL3_IMPL_AUTO
+  // where the two rules part (auto_mismatch): such a geometry is sized and launched with DL3_IMPL_GATHER.
   int im = impl;
-  if (im == DL3_IMPL_AUTO) im = (stride == 1 && Ho == H && Wo == W) ? DL3_IMPL_MARCH : DL3_IMPL_GATHER;
+  if (im == DL3_IMPL_AUTO) im = auto_sized_for_march(H, W, stride, Ho, Wo) ? DL3_IMPL_MARCH : DL3_IMPL_GATHER;
   // fwd and bwd gather plans differ in pixel count; report the larger so one buffer fits both
   DwPlan a = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, false);
   DwPlan b = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, true);
@@ -982,6 +996,9 @@ extern "C" int dl3_dwconv3x3_fwd(const float *x, const float *in_scale, const fl
   DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "dwconv3x3_fwd: scale/shift must come together");
   const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);
   DL3_UNSUPPORTED(im < 0, "dwconv3x3_fwd: march impl needs stride 1, pad == rate, Ho == H, Wo == W");
+  DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),
+                  "dwconv3x3_fwd: DL3_IMPL_AUTO sizes the partials of a stride-1 Ho == H, Wo == W geometry for the march kernels, "
+                  "pad (%d,%d) != rate %d needs the gather kernels: size and launch with DL3_IMPL_GATHER", pad_t, pad_l, rate);
   DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, false);
   hipStream_t st = (hipStream_t)stream;
   // the caller sized the partial buffer with dl3_dwconv3x3_partials (the larger of the forward and the backward
@@ -1020,6 +1037,9 @@ static int dwconv3x3_bwd_impl(const float *g, const float *yraw, const float *cA
   DL3_CHECK_ARG(!dstat_partial || (dx && x_mean && x_invstd), "dwconv3x3_bwd: dstat needs dx, x_mean, x_invstd");
   const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);
   DL3_UNSUPPORTED(im < 0, "dwconv3x3_bwd: march impl needs stride 1, pad == rate, Ho == H, Wo == W");
+  DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),
+                  "dwconv3x3_bwd: DL3_IMPL_AUTO sizes the partials of a stride-1 Ho == H, Wo == W geometry for the march kernels, "
+                  "pad (%d,%d) != rate %d needs the gather kernels: size and launch with DL3_IMPL_GATHER", pad_t, pad_l, rate);
   DL3_UNSUPPORTED(stat_x && im != DL3_IMPL_MARCH, "dwconv3x3_bwd_sx: sums against another tensor need the march kernel (stride 1, SAME)");
   DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, true);
   hipStream_t st = (hipStream_t)stream;

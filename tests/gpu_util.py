@@ -41,6 +41,42 @@ def dropout_keep_mask(seed, n, rate, step=0):
     return (u >= np.float32(rate)).astype(np.float32)
 
 
+BAND = 64                 # floats before and after every guarded output
+BAND_BITS = 0x4B3C2D1E    # a finite float pattern no kernel under test produces
+
+
+class Guarded:
+    """a device output of `shape` inside a larger buffer: BAND sentinel floats, the NaN payload, BAND sentinel floats"""
+
+    def __init__(self, pool, name, *shape):
+        self.name, self.n = name, int(np.prod(shape))
+        self.full = torch.empty(self.n + 2 * BAND, dtype=torch.float32, device="cuda")
+        self.full.view(torch.int32).fill_(BAND_BITS)
+        self.t = self.full[BAND:BAND + self.n].view(*shape)
+        self.t.fill_(float("nan"))
+        self.p = ptr(self.full, BAND)
+        _KEEP.append(self.full)
+        pool.append(self)
+
+    def bands_intact(self):
+        bits = self.full.view(torch.int32)
+        return bool((bits[:BAND] == BAND_BITS).all()) and bool((bits[BAND + self.n:] == BAND_BITS).all())
+
+    def unwritten(self):
+        return bool(torch.isnan(self.t).all())
+
+
+def assert_bands(pool):
+    torch.cuda.synchronize()
+    bad = [g.name for g in pool if not g.bands_intact()]
+    assert not bad, "wrote outside its output: %s" % bad
+
+
+def assert_untouched(pool):
+    assert_bands(pool)
+    assert all(g.unwritten() for g in pool), [g.name for g in pool if not g.unwritten()]
+
+
 def host(t):
     torch.cuda.synchronize()
     return t.cpu().numpy()

@@ -1,0 +1,242 @@
+"""CPU checks of the case table of tests/test_gpu_dwconv.py (tests/dwconv_cases.py): the float64 oracle the GPU tests
+compare with agrees with torch on every geometry of the table (stride 3, mixed, asymmetric and no padding included), the
+mask nudge does what it says, every case still sits on the path of csrc/dwconv.hip it was written for, the planner and the
+row loops restated in Python still restate the source, and DL3_IMPL_AUTO is refused exactly where its two rules part."""
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import dl3_oracle as O
+from tests import dwconv_cases as D
+
+HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "keras-segmentation-deeplab-v3.1_amd", "csrc",
+                   "dwconv.hip")
+BIG = 1 << 22   # geometries with more elements are checked against torch on 8 of their channels (the operation is per channel)
+
+
+def _small(g):
+    return g if g[0] * g[1] * g[2] * g[3] <= BIG else g[:3] + (8,) + g[4:]
+
+
+GEOMS = sorted({_small(c.geom) for c in D.CASES} | {_small(g) for g in D.AUTO_REFUSED + D.AUTO_TAKEN})
+FWD_KERNELS = ("dw_march_fwd", "dw_march2_fwd", "dw_gather_fwd")
+BWD_KERNELS = ("dw_march_bwd", "dw_gather_bwd", "dw_s2_bwd")
+
+
+def test_case_ids_are_unique_and_forms_are_consistent():
+    ids = [c.id for c in D.CASES]
+    assert len(ids) == len(set(ids))
+    for c in D.CASES:
+        N, H, W, C, stride, rate, pt, pl, Ho, Wo = c.geom
+        assert min(c.geom[:6]) >= 1 and Ho >= 1 and Wo >= 1 and C % 4 == 0, c.id
+        assert c.xform in ("none", "affine", "act", "affine+act") and c.grad in ("bn", "plain"), c.id
+        assert (c.act in (1, 2)) == c.xform.endswith("act"), c.id
+        assert c.shift == "normal" or c.xform.startswith("affine"), c.id
+        assert c.impl in (D.AUTO, D.GATHER, D.MARCH) and D.resolve_impl(c.impl, c.geom) > 0, c.id
+        assert not D.auto_mismatch(c.impl, c.geom), c.id                  # a case is a launch the library takes
+        assert c.dx or not (c.stats or c.add or c.sx), c.id               # dstat_partial needs dx
+        assert not c.sx or (c.stats and D.bwd_kernel(c) == "dw_march_bwd"), c.id
+        assert c.ppb is None or D.plan_of(c).impl == D.MARCH, c.id
+        # every output row the geometry names reads at least one input row: (Ho, Wo) is no larger than the padded input allows
+        assert (Ho - 1) * stride - pt < H and (Wo - 1) * stride - pl < W, c.id
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=lambda g: "x".join(map(str, g)))
+def test_oracle_depthwise_matches_torch(geom):
+    """O.depthwise3x3 forward, dx and dw in float64 against torch.nn.functional.conv2d(groups=C) + autograd on explicitly
+    padded input, cropped to (Ho, Wo): 1e-10 relative.  D.dw_abs_terms is the same sum over absolute values."""
+    N, H, W, C, s, r, pt, pl, Ho, Wo = geom
+    rng = np.random.default_rng(Ho * 1000 + Wo)
+    x = rng.normal(0, 1, (N, H, W, C))
+    w = rng.normal(0, 0.3, (3, 3, C))
+    g = rng.normal(0, 1, (N, Ho, Wo, C))
+    tape = O.Tape()
+    y = O.depthwise3x3(x, w, s, r, pt, pl, Ho, Wo, tape=tape)
+    grads = tape.backward(y, g)
+    xt = torch.from_numpy(x).permute(0, 3, 1, 2).requires_grad_(True)
+    wt = torch.from_numpy(w).permute(2, 0, 1).unsqueeze(1).requires_grad_(True)   # [C][1][3][3]
+    pb = max(0, (Ho - 1) * s + 2 * r + 1 - pt - H)
+    pr = max(0, (Wo - 1) * s + 2 * r + 1 - pl - W)
+    yt = F.conv2d(F.pad(xt, (pl, pr, pt, pb)), wt, stride=s, dilation=r, groups=C)[:, :, :Ho, :Wo]
+    assert yt.shape == (N, C, Ho, Wo)
+    yt.backward(torch.from_numpy(g).permute(0, 3, 1, 2))
+
+    def rel(a, b):
+        return float(np.abs(a - b).max() / np.abs(b).max())
+
+    assert rel(y, yt.detach().permute(0, 2, 3, 1).numpy()) < 1e-10
+    assert rel(grads[id(x)], xt.grad.permute(0, 2, 3, 1).numpy()) < 1e-10
+    assert rel(grads[id(w)], wt.grad[:, 0].permute(1, 2, 0).numpy()) < 1e-10
+    # the abs-term sums: the weight gradient of |x| and |g|
+    tape2 = O.Tape()
+    ax, ag = np.abs(x), np.abs(g)
+    ya = O.depthwise3x3(ax, w, s, r, pt, pl, Ho, Wo, tape=tape2)
+    ref = tape2.backward(ya, ag)[id(w)]
+    assert np.abs(D.dw_abs_terms(x, g, geom) - ref).max() <= 1e-10 * ref.max()
+
+
+@pytest.mark.parametrize("case", [c for c in D.CASES if c.xform.endswith("act")], ids=lambda c: c.id)
+def test_mask_nudge(case):
+    x, s, t, act, moved = D.draw_view(case)
+    assert act == case.act and x.dtype == np.float32 and x.shape == case.geom[:4]
+    z = D.preact(x, s, t)
+    for thr in D.thresholds(act):
+        assert np.abs(z - thr).min() >= D.MASK_MARGIN
+    assert moved < 0.01 * x.size
+    assert (z < 0).any() and (z > 0).any() and (act != 2 or (z > 6).any())
+    if case.shift == "positive":
+        assert (t >= 0.3).all() and (t <= 0.9).all()
+
+
+@pytest.mark.parametrize("case", D.CASES, ids=lambda c: c.id)
+def test_case_sits_on_its_branch(case):
+    assert case.branch
+    for tag in case.branch:
+        assert D.BRANCH[tag](case), (case.id, tag)
+
+
+def _seen(kernel, pred):
+    return any(pred(c) for c in D.CASES if kernel in (D.fwd_kernel(c), D.bwd_kernel(c)))
+
+
+def test_every_named_path_has_a_case():
+    assert {t for c in D.CASES for t in c.branch} == set(D.BRANCH)
+    assert {D.fwd_kernel(c) for c in D.CASES} == set(FWD_KERNELS) and {D.bwd_kernel(c) for c in D.CASES} == set(BWD_KERNELS)
+    for k in FWD_KERNELS + BWD_KERNELS:
+        assert _seen(k, lambda c: c.xform == "affine") and _seen(k, lambda c: c.xform == "act"), k
+    for k in BWD_KERNELS:
+        assert _seen(k, lambda c: c.grad == "plain") and _seen(k, lambda c: not c.dx), k
+        assert _seen(k, lambda c: c.dx and not c.add) and _seen(k, lambda c: c.dx and not c.stats), k
+        assert _seen(k, lambda c: c.add and not c.stats), k            # dstat_partial == NULL with dx_add
+        assert _seen(k, lambda c: c.grad == "plain" and c.stats), k    # cA == NULL with dstat_partial
+    for add in (False, True):   # sx with and without the addend, each on straight-line groups
+        assert any(c.sx and c.add == add and D.fast_groups(c, "dw_march_bwd") > 0 for c in D.CASES)
+    # dw_s2_bwd on C % 32 != 0 with each optional operand absent
+    rag = [c for c in D.CASES if D.BRANCH["s2-ragged-c"](c)]
+    assert any(c.grad == "plain" for c in rag) and any(c.dx and not c.add for c in rag) and any(not c.dx for c in rag)
+    # the loop cases run once each
+    for tag in ("gather-loop-bwd", "s2-loop"):
+        assert sum(D.BRANCH[tag](c) for c in D.CASES) == 1, tag
+
+
+def test_mirror_numbers_of_the_named_shapes():
+    """the plans and straight-line group counts the table was sized with"""
+    def case(geom, **kw):
+        return D._c("x", geom, (), **kw)
+
+    c = case(D.same(1, 24, 32, 32, 1, 3))
+    p = D.plan_of(c)
+    assert (p.fwd.two, p.fwd.nchunk, p.fwd.ppb, p.fwd.Kmax) == (0, 1, 1, 8) and D.fast_groups(c, "dw_march_fwd") == 3
+    c = case(D.same(1, 48, 40, 64, 1, 3))
+    p = D.plan_of(c)
+    assert (p.fwd.nchunk, p.fwd.TK, p.fwd.nxseg) == (2, 8, 2) and 40 % 32 != 0
+    assert all(w.fast == 1 for w in D.walk_of(c, "dw_march_fwd")) and len(D.walk_of(c, "dw_march_fwd")) == 6
+    c = case(D.same(1, 12, 32, 32, 1, 1))
+    assert D.plan_of(c).bwd.nchunk == 2 and [w.fast for w in D.walk_of(c, "dw_march_bwd")] == [2, 2]
+    assert D.fast_groups(c, "dw_march2_fwd") == 0                      # one 64-pixel segment, half of it outside
+    c = case(D.same(2, 20, 33, 64, 1, 2))
+    assert D.plan_of(c).bwd.nchunk == 2 and D.fast_groups(c, "dw_march_bwd") == 6
+    c = case(D.same(1, 20, 40, 40, 1, 8), ppb=3)
+    p = D.plan_of(c)
+    assert (p.fwd.two, p.fwd.ppb, p.fwd.ny, p.bwd.ppb) == (1, 3, 3, 3)
+    assert sorted({w.rows for w in D.walk_of(c, "dw_march2_fwd")}) == [2, 3]
+    # rate 2 on 20 x 64 x 32: Kmax 10 is cut into two 5-row chunks, and a chunked plan takes no DL3_DW_PPB; 16 rows are one
+    assert D.plan_of(case(D.same(1, 20, 64, 32, 1, 2), ppb=2)).fwd[6:9] == (5, 2, 1)
+    c = case(D.same(1, 16, 64, 32, 1, 2), ppb=2)
+    assert D.plan_of(c).fwd[5:10] == (8, 8, 1, 2, 1) and D.fast_groups(c, "dw_march2_fwd") == 2
+    p = D.plan_of(case(D.same(1, 40, 64, 32, 1, 32)))
+    assert (p.fwd.two, p.fwd.nphase, p.fwd.Kmax, p.fwd.ppb) == (1, 32, 2, 1)
+    assert all(xb == xa + 32 and xa % 64 < 32 for xa, xb in D._two_pixel_lanes(D.same(1, 40, 64, 32, 1, 32)))
+    g = D.padded(1, 33, 64, 2048, 1, 2, 2, 2)
+    assert g[8:] == (33, 64) and D.plans(g, D.GATHER).fwd.PB == 64 and g[1] * g[2] == 2112 > 32 * 64
+    g = D.same(1, 91, 91, 2048, 2, 1)
+    assert g[6:] == (1, 1, 46, 46) and D.plans(g, D.AUTO).bwd.PB == 64 and 46 * 46 > 2048
+    p = D.plans(D.same(2, 17, 65, 1376, 1, 16), D.AUTO)
+    assert (p.fwd.P, p.bwd.P, p.Pmax) == (64, 48, 64)
+    # an override below 1 or above the phase count is clamped; an unchunked plan of 12 or more rows ignores it
+    assert D.dw_plan(D.same(1, 20, 40, 40, 1, 8), D.MARCH, False, 0).ppb == 1
+    assert D.dw_plan(D.same(1, 20, 40, 40, 1, 8), D.MARCH, False, 99).ppb == 8
+    assert D.dw_plan(D.same(64, 12, 64, 512, 1, 1), D.MARCH, True, 3).ppb == 1
+
+
+def _kernel_text(src, name):
+    a = src.index("void %s(" % name)
+    return src[a:src.index("__global__", a)]
+
+
+def test_mirror_restates_the_source():
+    """the constants and conditions the Python mirror uses are the ones csrc/dwconv.hip is written with"""
+    src = re.sub(r"\s+", " ", open(HIP).read())
+    for text in ("p.nslab = dl3_cdiv(C, 32);",
+                 "p.two = (!bwd && 32 % rate == 0 && W >= 32) ? 1 : 0;",                       # the `two` rule
+                 "p.nxseg = dl3_cdiv(W, p.two ? 64 : 32);",
+                 "p.nphase = rate < H ? rate : H;",
+                 "const int Kmax = dl3_cdiv(H, rate);",
+                 "const long want = 1024;",
+                 "while (TK > 8 && (long)N * p.nslab * p.nxseg * p.nphase * dl3_cdiv(Kmax, TK) < want) TK = (TK + 1) / 2;",
+                 "if (p.nchunk == 1 && Kmax < 12) { ppb = 12 / Kmax; if (ppb > p.nphase) ppb = p.nphase;",
+                 "while (ppb > 1 && (long)N * p.nslab * p.nxseg * dl3_cdiv(p.nphase, ppb) < 2048) --ppb;",
+                 'if (const char *e = getenv("DL3_DW_PPB")) ppb = atoi(e);',
+                 "if (ppb > p.nphase) ppb = p.nphase; if (ppb < 1) ppb = 1; }",
+                 "p.ny = (ppb > 1) ? dl3_cdiv(p.nphase, ppb) : p.nphase * p.nchunk; p.P = N * p.ny * p.nxseg;",
+                 "const long NP = bwd ? (long)N * H * W : (long)N * Ho * Wo; long pb = (NP + 31) / 32; "
+                 "long cap = 4096 / p.nslab; if (cap < 1) cap = 1; if (pb > cap) pb = cap;",
+                 "return stride == 1 && pad_t == rate && pad_l == rate && Ho == H && Wo == W; }",     # march_ok
+                 "if (impl == DL3_IMPL_AUTO) return ok ? DL3_IMPL_MARCH : DL3_IMPL_GATHER; "
+                 "if (impl == DL3_IMPL_MARCH && !ok) return -1; return impl;",                      # resolve_impl
+                 "bool auto_sized_for_march(int H, int W, int stride, int Ho, int Wo) { return stride == 1 && Ho == H && Wo == W; }",
+                 "if (im == DL3_IMPL_AUTO) im = auto_sized_for_march(H, W, stride, Ho, Wo) ? DL3_IMPL_MARCH : DL3_IMPL_GATHER;",
+                 "return impl == DL3_IMPL_AUTO && im == DL3_IMPL_GATHER && auto_sized_for_march(H, W, stride, Ho, Wo);",
+                 "return a.P > b.P ? a.P : b.P;",
+                 "if (stride == 2 && rate == 1 && pad_t <= 1 && pad_l <= 1) hipLaunchKernelGGL(dw_s2_bwd,",   # the dw_s2_bwd dispatch
+                 "const int A = (G.H + G.pad_t + 1) / 2, Bn = (G.W + G.pad_l + 1) / 2;",
+                 "(C % 32 == 0) ? (march_fast() & 1) : 0", "(C % 32 == 0) ? (march_fast() & 2) : 0",
+                 "(C % 32 == 0) ? (march_fast() & 4) : 0", "return 7;"):
+        assert text in src, text
+    assert src.count("DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),") == 2      # forward and backward
+    fwd1, fwd2, bwd = (_kernel_text(src, k) for k in ("dw_march_fwd", "dw_march2_fwd", "dw_march_bwd"))
+    for text, R, seg, loop in ((fwd1, 4, 32, "kg + R - 1 <= ke"), (fwd2, 3, 64, "kg + R - 1 <= ke"), (bwd, 2, 32, "kg + R - 1 < k1")):
+        assert text.count("constexpr int R = ") == 1 and "constexpr int R = %d;" % R in text
+        assert "for (; %s; kg += R) group(kg, std::true_type{});" % loop in text
+        assert "for (; kg <= ke; kg += R) group(kg, std::false_type{});" in text
+        assert "const bool allact = fast && (slab * 32 + 32 <= C) && (xs * %d + %d <= W);" % (seg, seg) in text
+        assert "const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;" in text and "const bool bot_halo = k1 < Ka;" in text
+        assert "const int Ka = __builtin_amdgcn_readfirstlane((a < H) ? (H - a + r - 1) / r : 0);" in text
+        assert "int kg = ks; group(kg, std::false_type{}); kg += R;" in text
+    assert D.ROWS_PER_GROUP == {"dw_march_fwd": 4, "dw_march2_fwd": 3, "dw_march_bwd": 2}
+    assert "if (allact && dx) {" in bwd and "if (allact) {" in fwd1 and "if (allact) {" in fwd2
+    assert "const int xa = xs * 64 + (pl / r) * 2 * r + pl % r, xb = xa + r;" in fwd2
+
+
+def _sweep():
+    for N, H, W, stride, rate in itertools.product((1, 2), (8, 13), (8, 40), (1, 2, 3), (1, 2, 3)):
+        for pt, pl in itertools.product((0, 1, 2, 3), repeat=2):
+            for g in (D.same(N, H, W, 32, stride, rate)[:6] + (pt, pl) + D.same(N, H, W, 32, stride, rate)[8:],
+                      D.padded(N, H, W, 32, stride, rate, pt, pl)):
+                if g[8] >= 1 and g[9] >= 1:
+                    yield g
+
+
+def test_auto_is_refused_exactly_where_its_two_rules_part():
+    """dl3_dwconv3x3_partials(AUTO) counts march rows from (stride, Ho, Wo) alone, the launchers take the march kernels only
+    where the pads equal the rate as well: where the two part, the gather kernels would write more rows than were counted"""
+    g = D.AUTO_REFUSED[0]
+    assert g == (1, 16, 16, 32, 1, 1, 0, 0, 16, 16) and D.resolve_impl(D.AUTO, g) == D.GATHER
+    assert D.partials(g, D.AUTO) == 2 and D.dw_plan(g, D.GATHER, False).PB == 8 and D.dw_plan(g, D.GATHER, True).PB == 8
+    assert D.partials(g, D.GATHER) == 8
+    refused = 0
+    for g in itertools.chain(_sweep(), D.AUTO_REFUSED, D.AUTO_TAKEN, (c.geom for c in D.CASES)):
+        parts = D.auto_sized_for_march(g) != D.march_ok(g)
+        assert D.auto_mismatch(D.AUTO, g) == parts, g
+        assert not D.auto_mismatch(D.GATHER, g) and not D.auto_mismatch(D.MARCH, g), g
+        refused += parts
+        if not parts:   # what AUTO launches fits what AUTO counted
+            im = D.resolve_impl(D.AUTO, g)
+            assert max(D.dw_plan(g, im, False).P, D.dw_plan(g, im, True).P) == D.partials(g, D.AUTO), g
+    assert refused > 100
+    assert all(D.auto_mismatch(D.AUTO, g) for g in D.AUTO_REFUSED) and not any(D.auto_mismatch(D.AUTO, g) for g in D.AUTO_TAKEN)

@@ -12,17 +12,15 @@ import zlib
 
 import numpy as np
 import pytest
-import torch
 
 from oracle import dl3_oracle as O
 from tests import conv3x3_cases as C
-from tests.gpu_util import _KEEP, call, dev, host, np_act, np_mask, ptr, relerr, stream
+from tests.gpu_util import Guarded as _Guarded, assert_bands as _assert_bands, assert_untouched as _assert_untouched
+from tests.gpu_util import call, dev, host, np_act, np_mask, ptr, relerr, stream
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
 SUM_TOL = 1e-3
-BAND = 64                 # floats before and after every output
-BAND_BITS = 0x4B3C2D1E    # a finite float pattern no kernel of this file produces
 
 
 @pytest.fixture(scope="module")
@@ -30,33 +28,6 @@ def L():
     import dl3_amd  # noqa: F401
     from dl3_amd import capi
     return capi.lib()
-
-
-class _Guarded:
-    """a device output of `shape` inside a larger buffer: BAND sentinel floats, the NaN payload, BAND sentinel floats"""
-
-    def __init__(self, pool, name, *shape):
-        self.name, self.n = name, int(np.prod(shape))
-        self.full = torch.empty(self.n + 2 * BAND, dtype=torch.float32, device="cuda")
-        self.full.view(torch.int32).fill_(BAND_BITS)
-        self.t = self.full[BAND:BAND + self.n].view(*shape)
-        self.t.fill_(float("nan"))
-        self.p = ptr(self.full, BAND)
-        _KEEP.append(self.full)
-        pool.append(self)
-
-    def bands_intact(self):
-        bits = self.full.view(torch.int32)
-        return bool((bits[:BAND] == BAND_BITS).all()) and bool((bits[BAND + self.n:] == BAND_BITS).all())
-
-    def unwritten(self):
-        return bool(torch.isnan(self.t).all())
-
-
-def _assert_bands(pool):
-    torch.cuda.synchronize()
-    bad = [g.name for g in pool if not g.bands_intact()]
-    assert not bad, "wrote outside its output: %s" % bad
 
 
 def _sums(part, P, C_):
@@ -189,11 +160,6 @@ def _refusal_buffers(Cin, Cout, geom):
                 dw=_Guarded(pool, "dw", 4, 9 * Cin * Cout), dx=_Guarded(pool, "dx", N, H, W, Cin),
                 ws=_Guarded(pool, "workspace", 9 * Cin * Cout))
     return ins, outs, pool
-
-
-def _assert_untouched(pool):
-    _assert_bands(pool)
-    assert all(g.unwritten() for g in pool), [g.name for g in pool if not g.unwritten()]
 
 
 @pytest.mark.parametrize("Cout", [24, 40, 48])

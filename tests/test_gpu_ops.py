@@ -219,7 +219,7 @@ def test_dwconv_aspp_rates_forced_phases(L, rate, ppb, monkeypatch):
 
 
 def test_dwconv_bwd_plain_operand(L):
-    """cA == NULL (dY = g), no add, no stats, no dx"""
+    """cA == NULL (dY = g), no add, no stats; dx is written (the dx == NULL launch is in tests/test_gpu_dwconv.py)"""
     N, H, W, C = 2, 16, 16, 32
     rng = np.random.default_rng(2)
     x = rng.normal(0, 1, (N, H, W, C)).astype(np.float32)

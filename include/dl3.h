@@ -393,6 +393,40 @@ int dl3_topk_threshold(const float *v, int N, float p, int S, const unsigned lon
  * front of it used (it holds the counter, zeroed there). */
 int dl3_mine_weights(const float *v, const float *weights, const float *tau, const int *k, float *w_out, float *nnz_out,
                      void *ws, int N, void *stream);
+/* ---- soft-Jaccard term next to the training cross-entropy (csrc/jaccard.hip): CE + lambda * L_J ------
+ * Our own definition, mirroring utils.Jaccard (utils.py:139-157).  B images of HW pixels, C <= 32 classes (-4 above):
+ *   u = (w != 0 and label < C; weights NULL: w = 1), p = softmax(z) in fp32 (no renormalise, no clip), y the one-hot label;
+ *   I = sum u p y, S = sum u p, Y = sum u y, U = S + Y - I per (image, class); present = Y > 0, J = I / U;
+ *   n_c = #images that hold class c, n_legal = #classes with n_c > 0;
+ *   L_J = 1 - (1 / n_legal) sum_c (1 / n_c) sum_b J  (0, with a zero gradient, when n_legal = 0: an all-void batch).
+ * dl3_jaccard_sums_*: partials [B][P][3][C] (double; I, S, Y), P = dl3_jaccard_partials(B, HW); a workgroup never mixes
+ *   two images, a lane accumulates in double, the waves meet in a fixed order.  plain: materialised logits [B*HW][C];
+ *   bilinear: the low-resolution logits in front of the final resize, interpolated in registers with TF's stated weight —
+ *   the logits dl3_upsample_softmax_xent sees (HW = Ho * Wo).
+ * dl3_jaccard_coef: folds the partials in ascending order in double into sums [B][C][3] (I, S, Y), then
+ *   kappa = present / (n_c n_legal), coef [B][C][2] = (A, Bc) = (-kappa / U, kappa I / U^2) rounded to float once,
+ *   stats [4] (double) = (L_J, n_legal, lambda * L_J, -) and *loss_row (nullable) = (float)(lambda * L_J): an extra row of
+ *   the loss partials, so that dl3_reduce_partials returns CE + lambda * L_J.  lambda is the only value frozen in the
+ *   launch: everything else is read from device memory, so the launch replays in a captured graph.
+ * dl3_softmax_xent_jaccard / dl3_upsample_softmax_xent_jaccard: loss_partial and the cross-entropy gradient exactly as
+ *   dl3_softmax_xent / dl3_upsample_softmax_xent (operation for operation: with an all-zero coef the gradient is theirs
+ *   bit for bit), plus lambda u p_k (G_k - sum_c p_c G_c), G_c = A[b,c] where c is the pixel's label, else Bc[b,c].
+ *   loss_partial has dl3_jaccard_loss_partials(B, HW) entries and carries the cross-entropy alone.
+ * No atomics: two runs are bit-identical.  At most 65535 images of at most 2^30 pixels, 2^31 - 1 pixels in all (-1). */
+int dl3_jaccard_partials(int B, int HW);
+int dl3_jaccard_loss_partials(int B, int HW);
+int dl3_jaccard_sums_plain(const float *logits, const float *labels, const float *weights, double *partials, int B, int HW,
+                           int C, void *stream);
+int dl3_jaccard_sums_bilinear(const float *logits_lo, const float *labels, const float *weights, double *partials, int N,
+                              int Hi, int Wi, int Ho, int Wo, int C, void *stream);
+int dl3_jaccard_coef(const double *partials, int P, int B, int C, float lambda, double *sums, float *coef, double *stats,
+                     float *loss_row, void *stream);
+int dl3_softmax_xent_jaccard(const float *logits, const float *labels, const float *weights, const float *nnz,
+                             const float *coef, float lambda, float *dlogits, float *loss_partial, int B, int HW, int C,
+                             void *stream);
+int dl3_upsample_softmax_xent_jaccard(const float *logits_lo, const float *labels, const float *weights, const float *nnz,
+                                      const float *coef, float lambda, float *dlogits, float *loss_partial, int N, int Hi,
+                                      int Wi, int Ho, int Wo, int C, void *stream);
 /* out[i] = sum_p partial[p][i]  (fixed order) */
 int dl3_reduce_partials(const float *partial, int P, int n, float *out, void *stream);
 /* m folds in one launch, each bit-identical to its own dl3_reduce_partials call.  desc (device, int64 [m][5]): partial

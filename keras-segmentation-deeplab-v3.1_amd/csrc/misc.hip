@@ -6,16 +6,7 @@
 
 namespace {
 
-// Keras categorical_crossentropy clips the renormalised probability with tf.clip_by_value before the log
-// (utils.py:130 -> keras/backend/tensorflow_backend.py), and the gradient of clip_by_value is ZERO where its input lies
-// outside [1e-7, 1 - 1e-7]: a pixel whose true-class probability has left that interval has a constant loss and hands
-// no gradient to any logit; inside it the gradient is (p - onehot).  1.f inside (bounds included, as TF), 0.f outside.
-__device__ __forceinline__ float dl3_clip_pass(float q) { return (q >= 1e-7f && q <= 1.f - 1e-7f) ? 1.f : 0.f; }
-// The loss normaliser count(w != 0): an integer count in a single process, count_all / world under data parallelism
-// (fractional, below 1 when the global count is smaller than the world): only a zero count is replaced (no weight is
-// non-zero -> every term is zero anyway)
-#define DL3_NNZ_FLOOR 1e-20f
-
+// (Keras' clip rule dl3_clip_pass and the normaliser floor DL3_NNZ_FLOOR: tailmath.h)
 // (the TF1-legacy bilinear weights and lerps: tailmath.h; the resize kernels take the fused weight .w)
 __global__ __launch_bounds__(256) void resize_fwd_kernel(const float *__restrict__ x, int ldx,
                                                          const float *__restrict__ sc,

@@ -1,5 +1,6 @@
 // tailmath.h — the per-pixel arithmetic the output head's consumers share (device helpers only): misc.hip (resize and the
-// training loss tails), evaltail.hip (evaluation tail) and crfunary.hip (CRF unary) decode the same class scores.
+// training loss tails), evaltail.hip (evaluation tail), crfunary.hip (CRF unary), mine.hip and jaccard.hip (the fronts of the
+// mined and the soft-Jaccard loss) decode the same class scores.
 #pragma once
 #include "common.h"
 
@@ -67,6 +68,16 @@ struct SubpixelTile {
     return px * LP + (e / rr) * (rr + 1) + e % rr;
   }
 };
+
+// Keras categorical_crossentropy clips the renormalised probability with tf.clip_by_value before the log
+// (utils.py:130 -> keras/backend/tensorflow_backend.py), and the gradient of clip_by_value is ZERO where its input lies
+// outside [1e-7, 1 - 1e-7]: a pixel whose true-class probability has left that interval has a constant loss and hands
+// no gradient to any logit; inside it the gradient is (p - onehot).  1.f inside (bounds included, as TF), 0.f outside.
+__device__ __forceinline__ float dl3_clip_pass(float q) { return (q >= 1e-7f && q <= 1.f - 1e-7f) ? 1.f : 0.f; }
+// The loss normaliser count(w != 0): an integer count in a single process, count_all / world under data parallelism
+// (fractional, below 1 when the global count is smaller than the world): only a zero count is replaced (no weight is
+// non-zero -> every term is zero anyway)
+#define DL3_NNZ_FLOOR 1e-20f
 
 // end of a 256-thread workgroup of a loss kernel: the four waves' sums (wave_sum of the lanes' terms) in a fixed order
 __device__ __forceinline__ void block_loss_partial(float wsum, float *loss_part) {

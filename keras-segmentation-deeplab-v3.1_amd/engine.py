@@ -23,7 +23,7 @@ import torch
 
 from . import capi
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
-from .graph import check_mining, raw_pixels
+from .graph import check_jaccard, check_mining, raw_pixels
 from .head import Head
 
 _ACT = {"relu": ACT_RELU, "relu6": ACT_RELU6}
@@ -246,7 +246,7 @@ class View:
 class Engine:
     def __init__(self, model, batch, training, bn_mode="batch", dropout=True, seed=2, device=None, use_graph=True,
                  dw_impl=IMPL_AUTO, rank=None, bn_variance="keras224", external_nnz=False, opt_trainable=None, bn_update=None,
-                 mining=None):
+                 mining=None, jaccard=None):
         if not torch.cuda.is_available():
             raise capi.DL3Error("the dl3 engine needs a GPU (HIP device); there is no CPU fallback")
         self.lib = capi.lib()
@@ -270,6 +270,14 @@ class Engine:
         # hard-example mining: (top_k_percent_pixels, hard_example_mining_step) — the step trains on the k
         # largest per-pixel losses, k from the schedule and the device-side step counter; None / p == 1: today's plan
         self.mining = check_mining(mining) if training else None
+        # soft-Jaccard term: the step minimises CE + jaccard * L_J; None / 0: today's plan
+        self.jaccard = check_jaccard(jaccard) if training else None
+        if self.jaccard and self.mining:
+            raise ValueError("the soft-Jaccard loss and hard-example mining are separate losses and cannot be combined")
+        if self.jaccard and self.external_nnz:
+            raise ValueError("the soft-Jaccard loss cannot ride a data-parallel (external_nnz) engine: the optimizer "
+                             "finishes ONE gradient scale from the all-reduced count, and the Jaccard term has another "
+                             "normaliser")
         self.device = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
         self.use_graph = use_graph
         self.fold_tail = True   # the loss kernel folds its gradient rows onto the low-resolution columns (the full-resolution dlogits never exist)
@@ -963,6 +971,12 @@ class Engine:
         BatchNorm on it, where its shape query accepts (DL3_FUSE_SHUFFLE=0: never)"""
         h = self.head
         ok = h.v.C <= 32
+        if self.jaccard:
+            # this loss's own rule (§16): its kernels hold a pixel's logits in registers and come in two forms — a
+            # bilinear head is read as `bilinear`, everything else (the Subpixel head included) as `plain`
+            if not ok:
+                raise ValueError("the soft-Jaccard loss takes at most 32 classes, this head has %d" % h.v.C)
+            return h if h.form == "bilinear" else h.plain
         if ok and h.form == "shuffle":
             ok = (os.environ.get("DL3_FUSE_SHUFFLE", "1") != "0" and h.src.buf.expected == 1 and not h.src.buf.bns
                   and self.lib.dl3_shuffle_xent_partials(*h.dims("loss")) > 0)
@@ -1022,6 +1036,40 @@ class Engine:
         return (self.mine_v.cpu().numpy(), self.mine_w.cpu().numpy(), float(self.mine_tau[0].item()),
                 int(self.mine_k[0].item()), int(ws[self.MINE_WS_COUNT]))
 
+    JACCARD_OPS = ("dl3_jaccard_sums_plain", "dl3_jaccard_sums_bilinear", "dl3_jaccard_coef", "dl3_softmax_xent_jaccard",
+                   "dl3_upsample_softmax_xent_jaccard")
+
+    def _lower_jaccard(self, h, wsrc, g):
+        """the loss launches of CE + lambda * L_J: per-image sums from the source the loss kernel reads, the coefficient
+        table and lambda * L_J (an extra row of the loss partials, so that the one fold below returns the sum), then the
+        loss kernel with the Jaccard half added to the full-resolution gradient g.  lambda is the only frozen value."""
+        B, HW, C = h.sizes["images"]
+        P = self.lib.dl3_jaccard_partials(B, HW)
+        # doubles live in the float arena's buffers, two floats each (8-byte aligned: every allocation is)
+        self.jac_part, self.jac_sums, self.jac_stats = self.zeros(2 * B * P * 3 * C), self.zeros(2 * B * C * 3), self.zeros(8)
+        self.jac_coef = self.zeros(B * C * 2)
+        self.lossP = self.lib.dl3_jaccard_loss_partials(B, HW)
+        self.loss_part = self.zeros(self.lossP + 1)
+        self.op(self.ops_fwd, *h.launch("jaccard_sums", labels=ptr(self.labels), w=ptr(self.sweights),
+                                  out=ptr(self.jac_part)))
+        self.op(self.ops_fwd, "dl3_jaccard_coef", ptr(self.jac_part), P, B, C, self.jaccard, ptr(self.jac_sums),
+                ptr(self.jac_coef), ptr(self.jac_stats), ptr(self.loss_part, self.lossP))
+        self.op(self.ops_fwd, *h.launch("jaccard_loss", labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz),
+                                  coef=ptr(self.jac_coef), lam=self.jaccard, grad=ptr(g), part=ptr(self.loss_part)))
+        self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP + 1, 1, ptr(self.loss))
+
+    def jaccard_record(self):
+        """(sums [B,C,3] float64 (I, S, Y), coef [B,C,2] float32 (A, Bc), L_J, cross-entropy) of the last step, read back
+        (test-facing); the cross-entropy is the loss partials' own sum, the step's loss is it plus lambda * L_J"""
+        if not self.jaccard:
+            raise ValueError("jaccard_record: this engine was lowered without the soft-Jaccard loss")
+        torch.cuda.current_stream().synchronize()
+        B, HW, C = self.loss_head.sizes["images"]
+        part = self.loss_part.cpu().numpy()
+        return (self.jac_sums.view(torch.float64).cpu().numpy().reshape(B, C, 3),
+                self.jac_coef.cpu().numpy().reshape(B, C, 2), float(self.jac_stats.view(torch.float64)[0].item()),
+                float(part[:self.lossP].astype(np.float64).sum()))
+
     def _lower_backward(self):
         self._prune_gradients()
         v = self.logits_view
@@ -1040,7 +1088,12 @@ class Engine:
         # the full-resolution gradient never exists where a row of it fits the LDS: the loss kernel folds each output row
         # onto the low-resolution columns, the resize unit's backward folds the rows
         fold = h.form == "bilinear" and self.fold_tail and ((buf.W + 2 * h.src.buf.W) * C + 2 * buf.W) * 4 <= 65536
-        if h.form == "shuffle":     # the gradient of the Subpixel convolution's output, in its unshuffled layout
+        if self.jaccard:
+            # the full-resolution gradient in the logits buffer, whatever the head: the resize unit's ordinary backward
+            # (the phase shift's) takes it from there — no folded, no shuffle-fused form of this loss
+            buf.grad = g = self.empty(M * buf.ld)
+            self._lower_jaccard(h, wsrc, g)
+        elif h.form == "shuffle":     # the gradient of the Subpixel convolution's output, in its unshuffled layout
             h.src.buf.grad = g = self.empty(h.src.buf.M * h.src.buf.ld)
             self.lossP = self.lib.dl3_shuffle_xent_partials(*h.dims("loss"))
         elif fold:
@@ -1049,10 +1102,11 @@ class Engine:
         else:
             buf.grad = g = self.empty(M * buf.ld)
             self.lossP = self.lib.dl3_rows_partials(M)
-        self.loss_part = self.zeros(self.lossP)
-        self.op(self.ops_fwd, *h.launch("loss", fold, labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz), grad=ptr(g),
-                                  part=ptr(self.loss_part)))
-        self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP, 1, ptr(self.loss))
+        if not self.jaccard:
+            self.loss_part = self.zeros(self.lossP)
+            self.op(self.ops_fwd, *h.launch("loss", fold, labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz), grad=ptr(g),
+                                      part=ptr(self.loss_part)))
+            self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP, 1, ptr(self.loss))
         buf.done = 1
         assert buf.expected == 1
         # weight transposes for bwd-data, then the units in reverse

@@ -32,6 +32,17 @@ def check_mining(mining):
     return float(p), int(S)
 
 
+def check_jaccard(weight):
+    """jaccard_weight of the soft-Jaccard loss -> float lambda, or None where the term is off (None, 0); ValueError for
+    anything that is not a finite number >= 0"""
+    if weight is None:
+        return None
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.floating, np.integer)) \
+            or not 0.0 <= float(weight) <= float(np.finfo(np.float32).max):   # (the launch takes it as a float)
+        raise ValueError("jaccard_weight must be a finite number >= 0, got %r" % (weight,))
+    return float(weight) or None
+
+
 def raw_pixels(x):
     """raw 0-255 pixels as the package takes them: a device tensor or a uint8 array (decoded images) as it is, anything
     else as a float32 array (the reference's arrays)"""
@@ -498,6 +509,7 @@ class Model:
         # package's classes only); anything else raises here, not at the first step.  The rule and the clip settings sit
         # beside the hyper-parameter dict, which for Adam stays the five-key dict it always was
         rule, hyper, clipnorm, clipvalue = compile_optimizer(optimizer)
+        self._refuse_jaccard_dp(loss, self._dp)
         self._compiled = dict(optimizer=hyper, optimizer_object=optimizer, loss=loss, metrics=metrics,
                               sample_weight_mode=sample_weight_mode, rule=rule, clipnorm=clipnorm, clipvalue=clipvalue)
         # Keras 2.2.4 collects the weights the optimizer updates HERE (`_collected_trainable_weights`), and the layers'
@@ -530,6 +542,7 @@ class Model:
         gradient exchange through host memory (10-100x slower); strict=False, or DL3_DIST_BACKEND=gloo asked for explicitly,
         keeps the warning-and-gloo behaviour the functional tests use."""
         from .parallel import DataParallel
+        self._refuse_jaccard_dp((getattr(self, "_compiled", None) or {}).get("loss"), True)
         self._dp = dp if dp is not None else DataParallel(strict=strict)
         self._dp_synced = False
         return self
@@ -559,13 +572,31 @@ class Model:
         loss = (getattr(self, "_compiled", None) or {}).get("loss")
         return getattr(loss, "mining", None)
 
+    @staticmethod
+    def _refuse_jaccard_dp(loss, dp):
+        """compile(loss=utils.sparse_crossentropy_jaccard(...)) and distribute() exclude each other, in either order
+        (DESIGN.md §16): host-only, raised before any device call"""
+        if dp is not None and getattr(loss, "jaccard", None) is not None:
+            raise ValueError("the soft-Jaccard loss does not train under distribute(): a data-parallel engine finishes ONE "
+                             "gradient scale in the optimizer from the all-reduced count(w != 0), and the Jaccard term has a "
+                             "normaliser of its own; train on one GPU or compile the cross-entropy")
+
+    def _jaccard(self):
+        """lambda of a compile(loss=utils.sparse_crossentropy_jaccard(...)) whose term is on, else None (any other loss,
+        jaccard_weight == 0)"""
+        loss = (getattr(self, "_compiled", None) or {}).get("loss")
+        return getattr(loss, "jaccard", None)
+
     def _engine_key(self, batch, training, kw):
         """(cache key, constructor keywords) of the engine for (batch, mode, keywords): host-only.  A training engine's
-        key carries the trainable flags and, through the keywords, the mining settings of the compiled loss — a plan
-        lowered for one setting is never replayed for another; a loss that does not mine adds nothing to either."""
+        key carries the trainable flags and, through the keywords, the mining settings or the Jaccard weight of the
+        compiled loss — a plan lowered for one setting is never replayed for another; a loss that neither mines nor adds
+        the Jaccard term adds nothing to either."""
         kw = dict(kw)
         if training and "mining" not in kw and self._mining() is not None:
             kw["mining"] = self._mining()
+        if training and "jaccard" not in kw and self._jaccard() is not None:
+            kw["jaccard"] = self._jaccard()
         key = (int(batch), bool(training), tuple(sorted(kw.items())))
         if training:
             flags = self._training_flags()

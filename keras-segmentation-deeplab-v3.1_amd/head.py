@@ -2,8 +2,8 @@
 
 Three forms: `plain` — materialised logits; `bilinear` — the low-resolution logits in front of the final
 dl3_resize_bilinear_fwd; `shuffle` — the unshuffled Subpixel output in front of dl3_phase_shift.  Four kernel families take
-any of them.  Engine._lo_softmax decides the form once; each consumer admits it by a rule of its own or reads the same head
-as `plain`; KERNELS is the one place that names the entry points and their argument order."""
+any of them; the two of the soft-Jaccard loss (§16) take `plain` and `bilinear`.  Engine._lo_softmax decides the form
+once; each consumer admits it by a rule of its own or reads the same head as `plain`; KERNELS is the one place that names the entry points and their argument order."""
 
 _LOSS = ("src", "labels", "w", "nnz", "grad", "part", "dims")
 _EVAL = ("src", "labels", "w", "part", "loss", "nnz", "counts", "confusion", "mask")
@@ -18,6 +18,13 @@ KERNELS = {
     "pixel_xent": {"plain": ("dl3_pixel_xent_plain", ("src", "labels", "w", "out", "rows")),
                    "bilinear": ("dl3_pixel_xent_bilinear", ("src", "labels", "w", "out", "dims")),
                    "shuffle": ("dl3_pixel_xent_shuffle", ("src", "labels", "w", "out", "dims"))},
+    # the soft-Jaccard loss: per-image sums, then loss + full-resolution gradient (no folded, no shuffle form)
+    "jaccard_sums": {"plain": ("dl3_jaccard_sums_plain", ("src", "labels", "w", "out", "images")),
+                     "bilinear": ("dl3_jaccard_sums_bilinear", ("src", "labels", "w", "out", "dims"))},
+    "jaccard_loss": {"plain": ("dl3_softmax_xent_jaccard", ("src", "labels", "w", "nnz", "coef", "lam", "grad", "part",
+                                                            "images")),
+                     "bilinear": ("dl3_upsample_softmax_xent_jaccard", ("src", "labels", "w", "nnz", "coef", "lam", "grad",
+                                                                        "part", "dims"))},
     "eval_tail": {"plain": ("dl3_eval_tail_plain", _EVAL + ("images",)),
                   "bilinear": ("dl3_eval_tail_bilinear", _EVAL + ("dims",)),
                   "shuffle": ("dl3_eval_tail_shuffle", _EVAL + ("dims",))},

@@ -80,6 +80,54 @@ class sparse_crossentropy_top_k:
         return "sparse_crossentropy_top_k(%r, %r)" % (self.top_k_percent_pixels, self.hard_example_mining_step)
 
 
+class sparse_crossentropy_jaccard:
+    """Loss object for Model.compile(loss=...): sparse_crossentropy_ignoring_last_label plus jaccard_weight times a
+    differentiable (soft) Jaccard term L_J, evaluated on the device.  L_J is this package's own
+    definition, mirroring `Jaccard` above: with u = (sample weight != 0 and label not void) and p the softmax, per image
+    and class I = sum u p y, S = sum u p, Y = sum u y, J = I / (S + Y - I) where the class occurs (Y > 0); L_J = 1 - the
+    mean over the classes that occur anywhere of the mean of J over the images that hold the class (0 for an all-void
+    batch).  The sample weights reach the term as the mask u only; the cross-entropy keeps them as they are.
+    jaccard_weight = 0 switches the term off (the plain loss, bit for bit).  Calling the object on host arrays returns the
+    per-pixel cross-entropy, as the plain marker does.  Evaluation and prediction do not see the term: val_loss stays the
+    cross-entropy.  Not available under Model.distribute() or together with hard-example mining."""
+
+    def __init__(self, jaccard_weight=1.0):
+        G.check_jaccard(jaccard_weight)   # ValueError
+        self.jaccard_weight = float(jaccard_weight)
+        self.__name__ = "sparse_crossentropy_jaccard"
+
+    @property
+    def jaccard(self):
+        """lambda for the training engine; None where the term is off (jaccard_weight == 0)"""
+        return G.check_jaccard(self.jaccard_weight)
+
+    def jaccard_term(self, y_true, y_pred, sample_weight=None):
+        """L_J in numpy float64 from host arrays: y_true [B,HW,1] (void = C), y_pred [B,HW,C] probabilities,
+        sample_weight [B,HW] or None (w = 1)"""
+        p = np.asarray(y_pred, np.float64)
+        B, HW, C = p.shape
+        t = np.asarray(y_true).reshape(B, HW).astype(np.int64)
+        u = (t >= 0) & (t < C)
+        if sample_weight is not None:
+            u &= np.asarray(sample_weight).reshape(B, HW) != 0
+        y = (t[..., None] == np.arange(C)) & u[..., None]
+        pu = p * u[..., None]
+        I, S, Y = (pu * y).sum(1), pu.sum(1), y.sum(1).astype(np.float64)
+        present = Y > 0
+        if not present.any():
+            return 0.0
+        J = np.where(present, I / np.where(present, S + Y - I, 1.0), 0.0)
+        n_c = present.sum(0)
+        legal = n_c > 0
+        return float(1.0 - np.mean(J.sum(0)[legal] / n_c[legal]))
+
+    def __call__(self, y_true, y_pred):
+        return sparse_crossentropy_ignoring_last_label(y_true, y_pred)
+
+    def __repr__(self):
+        return "sparse_crossentropy_jaccard(%r)" % (self.jaccard_weight,)
+
+
 def sparse_accuracy_ignoring_last_label(y_true, y_pred):
     """utils.py:132-138 on host."""
     C = y_pred.shape[-1]

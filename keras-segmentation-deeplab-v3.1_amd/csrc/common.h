@@ -38,6 +38,20 @@ void dl3_set_error(const char *fmt, ...);
 
 static inline int dl3_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// workgroups of a grid-stride launch: one per per_block items, at least one, at most cap
+static inline int dl3_blocks(long n, int per_block, long cap) {
+  long b = (n + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+// M(MAXC) for the smallest register row that holds C <= 32 classes
+#define DL3_DISPATCH_MAXC(C, M) \
+  do {                          \
+    if ((C) <= 8) { M(8); }     \
+    else if ((C) <= 24) { M(24); } \
+    else { M(32); }             \
+  } while (0)
 
 // ---------------------------------------------------------------- device helpers
 // Branch-free activation: act is wave-uniform, so the clamp bounds are scalar selects and the activation is
@@ -99,8 +113,10 @@ __device__ __forceinline__ unsigned long long dl3_step_seed(unsigned long long s
   return step ? seed + step[0] * 0xD1B54A32D192ED03ull : seed;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-  // 64-lane butterfly
+// 64-lane butterfly: every lane ends with the same sum
+// (float, double, int, unsigned int: the types __shfl_xor moves)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int kMaxC = 32;    // dl3_crf_inference's label limit
+// (kHeadMaxC classes at most: dl3_crf_inference's label limit too)
 constexpr int kPix = 256;    // pixels per workgroup
 
 enum { kPlain = 0, kBilinear = 1, kShuffle = 2 };
@@ -32,17 +32,7 @@ template <int MAXC>
 __device__ __forceinline__ void unary_pixel(float (&z)[MAXC], int C, int is_prob, float scale, double unif, float clip) {
   double inv = 1.0;
   if (!is_prob) {
-    float mx = z[0];
-#pragma unroll
-    for (int c = 1; c < MAXC; c++)
-      if (c < C) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      z[c] = (c < C) ? expf(z[c] - mx) : 0.f;
-      s += z[c];
-    }
-    inv = 1.0 / (double)s;
+    inv = 1.0 / (double)softmax_exp<MAXC, float>(z, C);
   }
 #pragma unroll
   for (int c = 0; c < MAXC; c++) {
@@ -93,12 +83,8 @@ __global__ __launch_bounds__(kPix) void crf_unary_kernel(const float *__restrict
   } else if constexpr (FORM == kBilinear) {
     const int Hi = g.a, Wi = g.b, Wo = g.d;
     const int oy = i / Wo, ox = i - oy * Wo;
-    const Lerp ly = tf1_lerp(oy, g.sy, Hi), lx = tf1_lerp(ox, g.sx, Wi);
-    const float *xb = x + (size_t)b * Hi * Wi * C;
-    const float *tl = xb + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = xb + ((size_t)ly.lo * Wi + lx.hi) * C;
-    const float *bl = xb + ((size_t)ly.hi * Wi + lx.lo) * C, *br = xb + ((size_t)ly.hi * Wi + lx.hi) * C;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.w, ly.w);
+    const BilinearTaps taps(x + (size_t)b * Hi * Wi * C, oy, ox, g.sy, g.sx, Hi, Wi, C);
+    taps.load<MAXC>(z, C, taps.lx.w, taps.ly.w);   // dl3_resize_bilinear_fwd's weight
   } else {
     // out[n, ia*r+q, ib*r+p, ch] = u[n, ia, ib, ch*r*r + p*r + q]  (dl3_phase_shift)
     const int H = g.a, W = g.b, r = g.c, rr = r * r;
@@ -137,7 +123,7 @@ int launch(const char *who, const float *x, float *U, int B, int N, int C, Geom 
            void *stream) {
   DL3_CHECK_ARG(x && U, "%s: null pointer", who);
   DL3_CHECK_ARG(B > 0 && N > 0 && C > 0, "%s: B, N, C must be positive, got %d, %d, %d", who, B, N, C);
-  DL3_UNSUPPORTED(C > kMaxC, "%s: at most %d classes, got %d", who, kMaxC, C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "%s: at most %d classes, got %d", who, kHeadMaxC, C);
   // every index of the kernel fits an int, the batch fits grid.y
   DL3_CHECK_ARG(N <= (1 << 25) && B <= 65535, "%s: B = %d, N = %d is too large", who, B, N);
   DL3_CHECK_ARG(scale <= 1.f && clip < 1.f, "%s: scale must be <= 1 and clip < 1, got %g, %g", who, (double)scale,
@@ -152,9 +138,7 @@ int launch(const char *who, const float *x, float *U, int B, int N, int C, Geom 
 #define DL3_UNARY(MAXC)                                                                                              \
   hipLaunchKernelGGL((crf_unary_kernel<MAXC, FORM>), grid, block, lds, st, x, U, N, C, g, is_prob, scale, unif, clip, \
                      vec_in, vec_out)
-  if (C <= 8) DL3_UNARY(8);
-  else if (C <= 24) DL3_UNARY(24);
-  else DL3_UNARY(32);
+  DL3_DISPATCH_MAXC(C, DL3_UNARY);
 #undef DL3_UNARY
   DL3_LAUNCH_CHECK(who);
   return DL3_OK;

@@ -14,7 +14,6 @@
 namespace {
 
 constexpr int kMaxClasses = 255;   // dl3_seg_counts' limit; the plain form serves it
-constexpr int kFusedMaxC = 32;     // logits of a pixel in registers
 constexpr int kBand = 8;           // output rows per workgroup (bilinear form)
 constexpr int kStageBytes = 48 * 1024;
 
@@ -26,10 +25,6 @@ struct Acc {
   double lsum;
   int nz;
 };
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // one pixel with its C <= MAXC logits in registers: argmax (first maximum), loss term, histogram bins
 template <int MAXC>
@@ -41,26 +36,14 @@ __device__ __forceinline__ int eval_pixel(float (&z)[MAXC], int C, float labf, f
   for (int c = 1; c < MAXC; c++)
     if (c < C && z[c] > mx) { mx = z[c]; am = c; }
   if (am_given >= 0) am = am_given;   // bilinear form: the prediction comes from the bit-pinned logits
-  float ssum = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; c++) {
-    z[c] = (c < C) ? expf(z[c] - mx) : 0.f;
-    ssum += z[c];
-  }
-  const float inv = 1.f / ssum;
+  const float ssum = exp_sum<MAXC, float>(z, C, mx);
   const int t = (int)labf;
   const bool tok = (t >= 0 && t < C);
-  float psum = 0.f, pt = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; c++) {
-    z[c] *= inv;
-    psum += z[c];
-    pt = (c == t) ? z[c] : pt;
-  }
+  const ClassProbs p = class_probs<MAXC>(z, ssum, t);
   if (tok) {
     // Keras categorical_crossentropy on probabilities: renormalise, clip to [1e-7, 1-1e-7], -log
     // (the quotient and the logarithm in double: one of each per pixel, and the sum is then as good as its fp32 terms)
-    double q = (double)pt / (double)psum;
+    double q = (double)p.pt / (double)p.psum;
     q = fmin(fmax(q, 1e-7), 1.0 - 1e-7);
     a.lsum += -log(q) * (double)wf;
   }
@@ -79,9 +62,8 @@ __device__ __forceinline__ void flush(Acc a, const int *hist, int C, int n, doub
                                       long long *conf, bool conf_in_lds) {
   __shared__ double red[4];
   __shared__ int redn[4];
-  const double ls = wave_sum_d(a.lsum);
-  int nz = a.nz;
-  for (int o = 32; o >= 1; o >>= 1) nz += __shfl_xor(nz, o, 64);
+  const double ls = wave_sum(a.lsum);
+  const int nz = wave_sum(a.nz);
   if ((threadIdx.x & 63) == 0) {
     red[threadIdx.x >> 6] = ls;
     redn[threadIdx.x >> 6] = nz;
@@ -159,16 +141,15 @@ __global__ __launch_bounds__(256) void eval_bilinear_kernel(const float *__restr
 #pragma unroll
       for (int k = 0; k < VEC; k++) {
         const int ox = g * VEC + k;
-        const Lerp lx = tf1_lerp(ox, sx, Wi);
-        const float *tl = src + lx.lo * C, *tr = src + lx.hi * C;
-        const float *bl = src + (Wi + lx.lo) * C, *br = src + (Wi + lx.hi) * C;
+        const BilinearTaps taps(src, ly, ox, sx, Wi, C);
+        const Lerp &lx = taps.lx;
         float z[MAXC];
         float mmx = 0.f;
         int am = 0;
 #pragma unroll
         for (int c = 0; c < MAXC; c++) {
           const int cc = min(c, C - 1);
-          const float a0 = tl[cc], a1 = tr[cc], b0 = bl[cc], b1 = br[cc];
+          const float a0 = taps.tl[cc], a1 = taps.tr[cc], b0 = taps.bl[cc], b1 = taps.br[cc];
           const float zm = bilerp(a0, a1, b0, b1, lx.w, ly.w);   // dl3_resize_bilinear_fwd's value
           if (c == 0) mmx = zm;
           else if (c < C && zm > mmx) { mmx = zm; am = c; }
@@ -245,7 +226,7 @@ __global__ __launch_bounds__(256) void eval_plain_kernel(const float *__restrict
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int *hist = reinterpret_cast<int *>(smem);
   const int n = blockIdx.y;
-  const bool lds_conf = conf && C <= kFusedMaxC;
+  const bool lds_conf = conf && C <= kHeadMaxC;
   const int nh = 3 * C + (lds_conf ? C * C : 0);
   for (int i = threadIdx.x; i < nh; i += 256) hist[i] = 0;
   __syncthreads();
@@ -286,14 +267,11 @@ __global__ __launch_bounds__(64) void eval_fold_kernel(const double *__restrict_
   const double *p = part + (size_t)blockIdx.x * P;
   double s = 0.0;
   for (int i = threadIdx.x; i < P; i += 64) s += p[i];
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if (threadIdx.x == 0) loss_sum[blockIdx.x] = s;
 }
 
 inline int hist_ints(int C, bool conf) { return 3 * C + (conf ? C * C : 0); }
-
-// no more than ~1024 shuffled pixels per workgroup: enough workgroups per image to fill the device
-inline int shuffle_pb(int W, int C, int r) { return subpixel_tile_pixels(W, C, r, (1024 + r * r - 1) / (r * r)); }
 
 inline int plain_chunks(int HW) {
   int c = dl3_cdiv(HW, 256 * 4);
@@ -324,7 +302,7 @@ void begin(int *nnz, int *counts, int N, int C, hipStream_t st) {
 }  // namespace
 
 extern "C" int dl3_eval_tail_bilinear_partials(int N, int Hi, int Wi, int Ho, int Wo, int C) {
-  if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C > kFusedMaxC) return 0;
+  if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C > kHeadMaxC) return 0;
   if ((size_t)2 * Wi * C * 4 > (size_t)kStageBytes) return 0;
   return dl3_cdiv(Ho, kBand);
 }
@@ -332,7 +310,7 @@ extern "C" int dl3_eval_tail_bilinear_partials(int N, int Hi, int Wi, int Ho, in
 extern "C" int dl3_eval_tail_bilinear(const float *logits_lo, const float *labels, const float *weights, double *partials,
                                       double *loss_sum, int *nnz, int *counts, long long *confusion, int *mask, int N,
                                       int Hi, int Wi, int Ho, int Wo, int C, void *stream) {
-  int rc = check_common("eval_tail_bilinear", logits_lo, labels, partials, loss_sum, nnz, counts, N, C, kFusedMaxC);
+  int rc = check_common("eval_tail_bilinear", logits_lo, labels, partials, loss_sum, nnz, counts, N, C, kHeadMaxC);
   if (rc != DL3_OK) return rc;
   const int P = dl3_eval_tail_bilinear_partials(N, Hi, Wi, Ho, Wo, C);
   DL3_UNSUPPORTED(P <= 0, "eval_tail_bilinear: %dx%d -> %dx%d x %d is not supported by the fused form (use "
@@ -346,9 +324,9 @@ extern "C" int dl3_eval_tail_bilinear(const float *logits_lo, const float *label
 #define DL3_EVAL_BIL(MAXC, VEC)                                                                                      \
   hipLaunchKernelGGL((eval_bilinear_kernel<MAXC, VEC>), grid, dim3(256), lds, st, logits_lo, labels, weights, partials, \
                      nnz, counts, confusion, mask, Hi, Wi, Ho, Wo, C, sy, sx)
-  if (C <= 8) { if (vec) DL3_EVAL_BIL(8, 4); else DL3_EVAL_BIL(8, 1); }
-  else if (C <= 24) { if (vec) DL3_EVAL_BIL(24, 4); else DL3_EVAL_BIL(24, 1); }
-  else { if (vec) DL3_EVAL_BIL(32, 4); else DL3_EVAL_BIL(32, 1); }
+#define DL3_EVAL_BIL_VEC(MAXC) if (vec) DL3_EVAL_BIL(MAXC, 4); else DL3_EVAL_BIL(MAXC, 1)
+  DL3_DISPATCH_MAXC(C, DL3_EVAL_BIL_VEC);
+#undef DL3_EVAL_BIL_VEC
 #undef DL3_EVAL_BIL
   hipLaunchKernelGGL(eval_fold_kernel, dim3(N), dim3(64), 0, st, partials, P, loss_sum);
   DL3_LAUNCH_CHECK("eval_tail_bilinear");
@@ -356,7 +334,7 @@ extern "C" int dl3_eval_tail_bilinear(const float *logits_lo, const float *label
 }
 
 extern "C" int dl3_eval_tail_shuffle_partials(int N, int H, int W, int C, int r) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > kFusedMaxC || r <= 0) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > kHeadMaxC || r <= 0) return 0;
   const int pb = shuffle_pb(W, C, r);
   if (pb < 1) return 0;
   return H * dl3_cdiv(W, pb);
@@ -365,7 +343,7 @@ extern "C" int dl3_eval_tail_shuffle_partials(int N, int H, int W, int C, int r)
 extern "C" int dl3_eval_tail_shuffle(const float *u, const float *labels, const float *weights, double *partials,
                                      double *loss_sum, int *nnz, int *counts, long long *confusion, int *mask, int N,
                                      int H, int W, int C, int r, void *stream) {
-  int rc = check_common("eval_tail_shuffle", u, labels, partials, loss_sum, nnz, counts, N, C, kFusedMaxC);
+  int rc = check_common("eval_tail_shuffle", u, labels, partials, loss_sum, nnz, counts, N, C, kHeadMaxC);
   if (rc != DL3_OK) return rc;
   const int P = dl3_eval_tail_shuffle_partials(N, H, W, C, r);
   DL3_UNSUPPORTED(P <= 0, "eval_tail_shuffle: a pixel of %d x %d x %d floats does not fit the LDS tile (use phase_shift + "
@@ -378,9 +356,7 @@ extern "C" int dl3_eval_tail_shuffle(const float *u, const float *labels, const 
 #define DL3_EVAL_SHF(MAXC)                                                                                          \
   hipLaunchKernelGGL((eval_shuffle_kernel<MAXC>), grid, dim3(256), lds, st, u, labels, weights, partials, nnz, counts, \
                      confusion, mask, H, W, C, r, pb)
-  if (C <= 8) DL3_EVAL_SHF(8);
-  else if (C <= 24) DL3_EVAL_SHF(24);
-  else DL3_EVAL_SHF(32);
+  DL3_DISPATCH_MAXC(C, DL3_EVAL_SHF);
 #undef DL3_EVAL_SHF
   hipLaunchKernelGGL(eval_fold_kernel, dim3(N), dim3(64), 0, st, partials, P, loss_sum);
   DL3_LAUNCH_CHECK("eval_tail_shuffle");
@@ -401,7 +377,7 @@ extern "C" int dl3_eval_tail_plain(const float *logits, const float *labels, con
   const int P = plain_chunks(HW);
   hipStream_t st = (hipStream_t)stream;
   begin(nnz, counts, N, C, st);
-  const size_t lds = (size_t)hist_ints(C, confusion != nullptr && C <= kFusedMaxC) * 4;
+  const size_t lds = (size_t)hist_ints(C, confusion != nullptr && C <= kHeadMaxC) * 4;
   hipLaunchKernelGGL(eval_plain_kernel, dim3(P, N), dim3(256), lds, st, logits, labels, weights, partials, nnz, counts,
                      confusion, mask, HW, C);
   hipLaunchKernelGGL(eval_fold_kernel, dim3(N), dim3(64), 0, st, partials, P, loss_sum);

@@ -13,33 +13,11 @@
 
 namespace {
 
-constexpr int kMaxC = 32;   // logits of a pixel in registers
 constexpr int kMaxHW = 1 << 30;   // pixels of one image: the 32-bit pixel index plus a grid stride stays in range
 
+// a workgroup stays inside one image: B images share `total` workgroups of per_block pixels each
 inline int per_image_blocks(long HW, int per_block, int B, int total) {
-  long p = (HW + per_block - 1) / per_block;
-  const long cap = (total + B - 1) / B;
-  if (p > cap) p = cap;
-  if (p < 1) p = 1;
-  return (int)p;
-}
-
-// TF's stated weight fl(o * scale) - lo, the weight dl3_upsample_softmax_xent's loss interpolates with.  tf1_lerp's .wl
-// states it with the headers' __fmul_rn / __fsub_rn, which are plain operators: the compiler contracts them into the resize
-// kernel's fused form (.w) in one kernel and not in the next (it did in the sums pass).  Here contraction is off.
-__device__ __forceinline__ float stated_weight(int o, float scale, const Lerp &l) {
-#pragma clang fp contract(off)
-  const float f = (float)o * scale;
-  return f - (float)l.lo;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);   // 64-lane butterfly: every lane ends with the same sum
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  return dl3_blocks(HW, per_block, (total + B - 1) / B);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -65,25 +43,26 @@ __global__ __launch_bounds__(256) void jaccard_sums_kernel(const float *__restri
     const float w = wgt ? wgt[i] : 1.f;
     if (!(t >= 0 && t < C) || w == 0.f) continue;   // u = 0: nothing to add (NaN weights count, as in dl3_count_nonzero)
     float z[MAXC];
+    // (own text on purpose, here and in the loss kernel below: with tailmath.h's BilinearTaps / softmax_exp / xent_pixel
+    // the bilinear instantiations of both measured 2 - 4 % slower; as written they compile to the streams they had)
     if (UPSAMPLE) {
       const int oy = i / Wo, ox = i - oy * Wo;
       const Lerp ly = tf1_lerp(oy, sy, Hi), lx = tf1_lerp(ox, sx, Wi);
       const float *s = x + (size_t)b * Hi * Wi * C;
       const float *tl = s + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = s + ((size_t)ly.lo * Wi + lx.hi) * C;
       const float *bl = s + ((size_t)ly.hi * Wi + lx.lo) * C, *br = s + ((size_t)ly.hi * Wi + lx.hi) * C;
-      const float wx = stated_weight(ox, sx, lx), wy = stated_weight(oy, sy, ly);
 #pragma unroll
-      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, wx, wy);
+      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.wl, ly.wl);
     } else {
       const float *r = x + ((size_t)b * HW + i) * C;
 #pragma unroll
       for (int c = 0; c < MAXC; c++) z[c] = r[min(c, C - 1)];
     }
+    // the exponentials are fp32; their sum and the quotient are double (the accumulators are anyway: one fused
+    // multiply-add per class where an add would stand), so p enters the sums without a rounding of its own
     float mx = z[0];
 #pragma unroll
     for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
-    // the exponentials are fp32; their sum and the quotient are double (the accumulators are anyway: one fused
-    // multiply-add per class where an add would stand), so p enters the sums without a rounding of its own
     double ssum = 0.0;
 #pragma unroll
     for (int c = 0; c < MAXC; c++) {
@@ -101,8 +80,8 @@ __global__ __launch_bounds__(256) void jaccard_sums_kernel(const float *__restri
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int c = 0; c < MAXC; c++) {
-    const double i_ = wave_sum_f64(accI[c]), s_ = wave_sum_f64(accS[c]);
-    const int y_ = wave_sum_i32(accY[c]);
+    const double i_ = wave_sum(accI[c]), s_ = wave_sum(accS[c]);
+    const int y_ = wave_sum(accY[c]);
     if (lane == 0) {
       red[wv][c] = i_;
       red[wv][MAXC + c] = s_;
@@ -134,8 +113,8 @@ __global__ __launch_bounds__(128) void jaccard_fold_kernel(const double *__restr
 __global__ __launch_bounds__(256) void jaccard_coef_kernel(const double *__restrict__ sums, float *__restrict__ coef,
                                                            double *__restrict__ stats, float *__restrict__ loss_row,
                                                            float lambda, int B, int C) {
-  __shared__ double cls[kMaxC];
-  __shared__ int ncls[kMaxC];
+  __shared__ double cls[kHeadMaxC];
+  __shared__ int ncls[kHeadMaxC];
   __shared__ int s_legal;
   if (threadIdx.x < C) {
     const int c = threadIdx.x;
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(256) void xent32_jaccard_kernel(const float *__rest
                                                              float lambda, float *__restrict__ dl,
                                                              float *__restrict__ loss_part, int HW, int C, int Hi, int Wi,
                                                              int Wo, float sy, float sx) {
-  constexpr int MAXC = kMaxC;
+  constexpr int MAXC = kHeadMaxC;
   __shared__ float tile[256 * MAXC];
   __shared__ float cA[MAXC], cB[MAXC];
   __shared__ float red[4];
@@ -223,9 +202,8 @@ __global__ __launch_bounds__(256) void xent32_jaccard_kernel(const float *__rest
       const float *s = x + (size_t)b * Hi * Wi * C;
       const float *tl = s + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = s + ((size_t)ly.lo * Wi + lx.hi) * C;
       const float *bl = s + ((size_t)ly.hi * Wi + lx.lo) * C, *br = s + ((size_t)ly.hi * Wi + lx.hi) * C;
-      const float wx = stated_weight(ox, sx, lx), wy = stated_weight(oy, sy, ly);
 #pragma unroll
-      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, wx, wy);
+      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.wl, ly.wl);
     } else {
       for (int j = threadIdx.x; j < nrem; j += 256) tile[j] = x[row0 + j];
       __syncthreads();
@@ -294,10 +272,19 @@ int launch_sums(const float *x, const float *labels, const float *weights, doubl
 #define DL3_JSUMS(MAXC)                                                                                               \
   hipLaunchKernelGGL((jaccard_sums_kernel<MAXC, UPSAMPLE>), grid, dim3(256), 0, st, x, labels, weights, partials, HW, C, \
                      Hi, Wi, Wo, sy, sx)
-  if (C <= 8) DL3_JSUMS(8);
-  else if (C <= 24) DL3_JSUMS(24);
-  else DL3_JSUMS(32);
+  DL3_DISPATCH_MAXC(C, DL3_JSUMS);
 #undef DL3_JSUMS
+  return DL3_OK;
+}
+
+// B images of HW pixels: B fits grid.y, a pixel index plus a grid stride and the flat index B * HW fit 32 bits
+int check_images(const char *who, int B, long HW) {
+  DL3_CHECK_ARG(B <= 65535 && HW <= kMaxHW && B * HW <= 0x7fffffffL, "%s: %d images of %ld pixels exceed the grid", who, B,
+                HW);
+  return DL3_OK;
+}
+int check_lambda(const char *who, float lambda) {
+  DL3_CHECK_ARG(lambda >= 0.f && lambda <= 3.4e38f, "%s: lambda must be finite and >= 0, got %g", who, (double)lambda);
   return DL3_OK;
 }
 
@@ -309,8 +296,8 @@ extern "C" int dl3_jaccard_loss_partials(int B, int HW) { return (B > 0 && HW > 
 extern "C" int dl3_jaccard_sums_plain(const float *logits, const float *labels, const float *weights, double *partials,
                                       int B, int HW, int C, void *stream) {
   DL3_CHECK_ARG(logits && labels && partials && B > 0 && HW > 0 && C > 0, "jaccard_sums_plain: bad argument");
-  DL3_CHECK_ARG(B <= 65535 && HW <= kMaxHW && (long)B * HW <= 0x7fffffffL, "jaccard_sums_plain: %d images of %d pixels exceed the grid", B, HW);
-  DL3_UNSUPPORTED(C > kMaxC, "jaccard_sums_plain: C=%d > 32", C);
+  if (int rc = check_images("jaccard_sums_plain", B, HW)) return rc;
+  DL3_UNSUPPORTED(C > kHeadMaxC, "jaccard_sums_plain: C=%d > 32", C);
   launch_sums<false>(logits, labels, weights, partials, B, HW, C, 0, 0, 0, 0.f, 0.f, (hipStream_t)stream);
   DL3_LAUNCH_CHECK("jaccard_sums_plain");
   return DL3_OK;
@@ -320,9 +307,8 @@ extern "C" int dl3_jaccard_sums_bilinear(const float *logits_lo, const float *la
                                          double *partials, int N, int Hi, int Wi, int Ho, int Wo, int C, void *stream) {
   DL3_CHECK_ARG(logits_lo && labels && partials && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0,
                 "jaccard_sums_bilinear: bad argument");
-  DL3_CHECK_ARG(N <= 65535 && (long)Ho * Wo <= kMaxHW && (long)N * Ho * Wo <= 0x7fffffffL, "jaccard_sums_bilinear: %d images of %d x %d pixels exceed the grid",
-                N, Ho, Wo);
-  DL3_UNSUPPORTED(C > kMaxC, "jaccard_sums_bilinear: C=%d > 32 (use resize_bilinear_fwd + jaccard_sums_plain)", C);
+  if (int rc = check_images("jaccard_sums_bilinear", N, (long)Ho * Wo)) return rc;
+  DL3_UNSUPPORTED(C > kHeadMaxC, "jaccard_sums_bilinear: C=%d > 32 (use resize_bilinear_fwd + jaccard_sums_plain)", C);
   const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
   launch_sums<true>(logits_lo, labels, weights, partials, N, Ho * Wo, C, Hi, Wi, Wo, sy, sx, (hipStream_t)stream);
   DL3_LAUNCH_CHECK("jaccard_sums_bilinear");
@@ -332,8 +318,8 @@ extern "C" int dl3_jaccard_sums_bilinear(const float *logits_lo, const float *la
 extern "C" int dl3_jaccard_coef(const double *partials, int P, int B, int C, float lambda, double *sums, float *coef,
                                 double *stats, float *loss_row, void *stream) {
   DL3_CHECK_ARG(partials && sums && coef && stats && P > 0 && B > 0 && C > 0, "jaccard_coef: bad argument");
-  DL3_CHECK_ARG(lambda >= 0.f && lambda <= 3.4e38f, "jaccard_coef: lambda must be finite and >= 0, got %g", (double)lambda);
-  DL3_UNSUPPORTED(C > kMaxC, "jaccard_coef: C=%d > 32", C);
+  if (int rc = check_lambda("jaccard_coef", lambda)) return rc;
+  DL3_UNSUPPORTED(C > kHeadMaxC, "jaccard_coef: C=%d > 32", C);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(jaccard_fold_kernel, dim3(B), dim3(128), 0, st, partials, sums, P, C);
   hipLaunchKernelGGL(jaccard_coef_kernel, dim3(1), dim3(256), 0, st, sums, coef, stats, loss_row, lambda, B, C);
@@ -346,9 +332,9 @@ extern "C" int dl3_softmax_xent_jaccard(const float *logits, const float *labels
                                         int HW, int C, void *stream) {
   DL3_CHECK_ARG(logits && labels && nnz && coef && dlogits && loss_partial && B > 0 && HW > 0 && C > 0,
                 "softmax_xent_jaccard: bad argument");
-  DL3_CHECK_ARG(B <= 65535 && HW <= kMaxHW && (long)B * HW <= 0x7fffffffL, "softmax_xent_jaccard: %d images of %d pixels exceed the grid", B, HW);
-  DL3_CHECK_ARG(lambda >= 0.f && lambda <= 3.4e38f, "softmax_xent_jaccard: lambda must be finite and >= 0, got %g", (double)lambda);
-  DL3_UNSUPPORTED(C > kMaxC, "softmax_xent_jaccard: C=%d > 32", C);
+  if (int rc = check_images("softmax_xent_jaccard", B, HW)) return rc;
+  if (int rc = check_lambda("softmax_xent_jaccard", lambda)) return rc;
+  DL3_UNSUPPORTED(C > kHeadMaxC, "softmax_xent_jaccard: C=%d > 32", C);
   hipLaunchKernelGGL((xent32_jaccard_kernel<false>), dim3(loss_blocks(B, HW), B), dim3(256), 0, (hipStream_t)stream, logits,
                      labels, weights, nnz, coef, lambda, dlogits, loss_partial, HW, C, 0, 0, 0, 0.f, 0.f);
   DL3_LAUNCH_CHECK("softmax_xent_jaccard");
@@ -362,11 +348,9 @@ extern "C" int dl3_upsample_softmax_xent_jaccard(const float *logits_lo, const f
   DL3_CHECK_ARG(logits_lo && labels && nnz && coef && dlogits && loss_partial && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 &&
                     Wo > 0 && C > 0,
                 "upsample_softmax_xent_jaccard: bad argument");
-  DL3_CHECK_ARG(N <= 65535 && (long)Ho * Wo <= kMaxHW && (long)N * Ho * Wo <= 0x7fffffffL,
-                "upsample_softmax_xent_jaccard: %d images of %d x %d pixels exceed the grid", N, Ho, Wo);
-  DL3_CHECK_ARG(lambda >= 0.f && lambda <= 3.4e38f, "upsample_softmax_xent_jaccard: lambda must be finite and >= 0, got %g",
-                (double)lambda);
-  DL3_UNSUPPORTED(C > kMaxC, "upsample_softmax_xent_jaccard: C=%d > 32", C);
+  if (int rc = check_images("upsample_softmax_xent_jaccard", N, (long)Ho * Wo)) return rc;
+  if (int rc = check_lambda("upsample_softmax_xent_jaccard", lambda)) return rc;
+  DL3_UNSUPPORTED(C > kHeadMaxC, "upsample_softmax_xent_jaccard: C=%d > 32", C);
   const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
   const int HW = Ho * Wo;
   hipLaunchKernelGGL((xent32_jaccard_kernel<true>), dim3(loss_blocks(N, HW), N), dim3(256), 0, (hipStream_t)stream,

@@ -13,7 +13,6 @@
 
 namespace {
 
-constexpr int kFusedMaxC = 32;   // logits of a pixel in registers
 constexpr int kBins = 2048;      // bins of the widest digit (11 bits): 8 KB of LDS per workgroup
 constexpr int kHistThreads = 1024;
 // workspace (32-bit words): 16 words of state, then the three digit histograms
@@ -38,9 +37,9 @@ __device__ __forceinline__ float finish_pixel(float et, double ssum, float wf) {
 template <int MAXC>
 __device__ __forceinline__ float pixel_loss(float (&z)[MAXC], int C, float labf, float wf) {
   const int t = (int)labf;
-  float mx = z[0];
-#pragma unroll
-  for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
+  const float mx = logit_max<MAXC>(z, C);
+  // (not softmax_exp: only the label's exponential is kept, so that the others need no register past the sum — kept in
+  // place for a later select, they cost pixel_shuffle_kernel<32> 15 VGPRs and its 64-register step)
   double ssum = 0.0;
   float et = 0.f;
 #pragma unroll
@@ -80,16 +79,10 @@ __global__ __launch_bounds__(256) void pixel_bilinear_kernel(const float *__rest
                                                              long M, int C, int Hi, int Wi, int Ho, int Wo, float sy,
                                                              float sx) {
   for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) {
-    const int ox = (int)(m % Wo);
-    const long q = m / Wo;
-    const int oy = (int)(q % Ho), n = (int)(q / Ho);
-    const Lerp ly = tf1_lerp(oy, sy, Hi), lx = tf1_lerp(ox, sx, Wi);
-    const float *b = x + (size_t)n * Hi * Wi * C;
-    const float *tl = b + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = b + ((size_t)ly.lo * Wi + lx.hi) * C;
-    const float *bl = b + ((size_t)ly.hi * Wi + lx.lo) * C, *br = b + ((size_t)ly.hi * Wi + lx.hi) * C;
+    const PixelPos p = split_pixel(m, Ho, Wo);
+    const BilinearTaps taps(x + (size_t)p.n * Hi * Wi * C, p.oy, p.ox, sy, sx, Hi, Wi, C);
     float z[MAXC];
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.wl, ly.wl);
+    taps.load<MAXC>(z, C, taps.lx.wl, taps.ly.wl);
     v[m] = pixel_loss<MAXC>(z, C, labels[m], weights ? weights[m] : 1.f);
   }
 }
@@ -123,16 +116,6 @@ __global__ __launch_bounds__(256) void pixel_shuffle_kernel(const float *__restr
     for (int c = 0; c < MAXC; c++) z[c] = tp[min(c, C - 1) * (rr + 1)];
     v[m] = pixel_loss<MAXC>(z, C, labels[m], weights ? weights[m] : 1.f);
   }
-}
-
-// no more than ~1024 shuffled pixels per workgroup (the evaluation tail's rule)
-inline int shuffle_pb(int W, int C, int r) { return subpixel_tile_pixels(W, C, r, (1024 + r * r - 1) / (r * r)); }
-
-inline int stream_blocks(long n, int per_block, int cap) {
-  long b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -276,7 +259,7 @@ __global__ __launch_bounds__(256) void mine_weights_kernel(const float *__restri
     wout[i] = m ? (w ? w[i] : 1.f) : 0.f;
     c += m;
   }
-  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -294,7 +277,7 @@ __global__ void mine_count_kernel(const unsigned int *__restrict__ ws, float *__
 extern "C" int dl3_pixel_xent_plain(const float *logits, const float *labels, const float *weights, float *v, int M,
                                     int C, void *stream) {
   DL3_CHECK_ARG(logits && labels && v && M > 0 && C > 0, "pixel_xent_plain: bad argument");
-  hipLaunchKernelGGL(pixel_plain_kernel, dim3(stream_blocks(M, 256, 8192)), dim3(256), 0, (hipStream_t)stream, logits,
+  hipLaunchKernelGGL(pixel_plain_kernel, dim3(dl3_blocks(M, 256, 8192)), dim3(256), 0, (hipStream_t)stream, logits,
                      labels, weights, v, (long)M, C);
   DL3_LAUNCH_CHECK("pixel_xent_plain");
   return DL3_OK;
@@ -304,17 +287,15 @@ extern "C" int dl3_pixel_xent_bilinear(const float *logits_lo, const float *labe
                                        int Hi, int Wi, int Ho, int Wo, int C, void *stream) {
   DL3_CHECK_ARG(logits_lo && labels && v && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0,
                 "pixel_xent_bilinear: bad argument");
-  DL3_UNSUPPORTED(C > kFusedMaxC, "pixel_xent_bilinear: C=%d > 32 (use resize_bilinear_fwd + pixel_xent_plain)", C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "pixel_xent_bilinear: C=%d > 32 (use resize_bilinear_fwd + pixel_xent_plain)", C);
   const long M = (long)N * Ho * Wo;
   DL3_CHECK_ARG(M <= 0x7fffffffL, "pixel_xent_bilinear: %ld pixels exceed 2^31 - 1", M);
   const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
-  dim3 grid(stream_blocks(M, 256, 16384));
+  dim3 grid(dl3_blocks(M, 256, 16384));
 #define DL3_PIX_BIL(MAXC)                                                                                            \
   hipLaunchKernelGGL((pixel_bilinear_kernel<MAXC>), grid, dim3(256), 0, (hipStream_t)stream, logits_lo, labels, weights, \
                      v, M, C, Hi, Wi, Ho, Wo, sy, sx)
-  if (C <= 8) DL3_PIX_BIL(8);
-  else if (C <= 24) DL3_PIX_BIL(24);
-  else DL3_PIX_BIL(32);
+  DL3_DISPATCH_MAXC(C, DL3_PIX_BIL);
 #undef DL3_PIX_BIL
   DL3_LAUNCH_CHECK("pixel_xent_bilinear");
   return DL3_OK;
@@ -323,7 +304,7 @@ extern "C" int dl3_pixel_xent_bilinear(const float *logits_lo, const float *labe
 extern "C" int dl3_pixel_xent_shuffle(const float *u, const float *labels, const float *weights, float *v, int N, int H,
                                       int W, int C, int r, void *stream) {
   DL3_CHECK_ARG(u && labels && v && N > 0 && H > 0 && W > 0 && C > 0 && r > 0, "pixel_xent_shuffle: bad argument");
-  DL3_UNSUPPORTED(C > kFusedMaxC, "pixel_xent_shuffle: C=%d > 32 (use phase_shift + pixel_xent_plain)", C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "pixel_xent_shuffle: C=%d > 32 (use phase_shift + pixel_xent_plain)", C);
   const int pb = shuffle_pb(W, C, r);
   DL3_UNSUPPORTED(pb < 1, "pixel_xent_shuffle: a pixel of %d x %d x %d floats does not fit the LDS tile", C, r, r);
   DL3_CHECK_ARG((long)N * H * r * W * r <= 0x7fffffffL, "pixel_xent_shuffle: more than 2^31 - 1 pixels");
@@ -332,9 +313,7 @@ extern "C" int dl3_pixel_xent_shuffle(const float *u, const float *labels, const
 #define DL3_PIX_SHF(MAXC)                                                                                          \
   hipLaunchKernelGGL((pixel_shuffle_kernel<MAXC>), grid, dim3(256), lds, (hipStream_t)stream, u, labels, weights, v, H, \
                      W, C, r, pb)
-  if (C <= 8) DL3_PIX_SHF(8);
-  else if (C <= 24) DL3_PIX_SHF(24);
-  else DL3_PIX_SHF(32);
+  DL3_DISPATCH_MAXC(C, DL3_PIX_SHF);
 #undef DL3_PIX_SHF
   DL3_LAUNCH_CHECK("pixel_xent_shuffle");
   return DL3_OK;
@@ -351,7 +330,7 @@ extern "C" int dl3_topk_threshold(const float *v, int N, float p, int S, const u
   hipStream_t st = (hipStream_t)stream;
   unsigned int *w = (unsigned int *)ws;
   // one workgroup of 1024 threads per CU or two: few workgroups keep the global atomics per pass low (bins x workgroups)
-  dim3 hgrid(stream_blocks(N, kHistThreads * 8, 512));
+  dim3 hgrid(dl3_blocks(N, kHistThreads * 8, 512));
   hipLaunchKernelGGL(mine_zero_kernel, dim3(dl3_cdiv(kWsWords, 256)), dim3(256), 0, st, w);
   hipLaunchKernelGGL(mine_hist_kernel<0>, hgrid, dim3(kHistThreads), 0, st, v, (long)N, w);
   hipLaunchKernelGGL(mine_pick_kernel<0>, dim3(1), dim3(256), 0, st, w, p, S, step, (long)N, k, tau);
@@ -368,7 +347,7 @@ extern "C" int dl3_mine_weights(const float *v, const float *weights, const floa
   DL3_CHECK_ARG(v && tau && k && w_out && nnz_out && ws && N > 0, "mine_weights: bad argument");
   hipStream_t st = (hipStream_t)stream;
   unsigned int *w = (unsigned int *)ws;
-  hipLaunchKernelGGL(mine_weights_kernel, dim3(stream_blocks(N, 256 * 8, 2048)), dim3(256), 0, st, v, weights, tau, k,
+  hipLaunchKernelGGL(mine_weights_kernel, dim3(dl3_blocks(N, 256 * 8, 2048)), dim3(256), 0, st, v, weights, tau, k,
                      w_out, w, (long)N);
   hipLaunchKernelGGL(mine_count_kernel, dim3(1), dim3(1), 0, st, w, nnz_out);
   DL3_LAUNCH_CHECK("mine_weights");

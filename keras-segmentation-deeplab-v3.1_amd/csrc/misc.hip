@@ -212,34 +212,11 @@ __global__ __launch_bounds__(256) void shuffle_xent_kernel(const float *__restri
     float z[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; c++) z[c] = cell[min(c, C - 1) * (rr + 1)];
-    float mx = z[0];
-#pragma unroll
-    for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
-    float ssum = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      z[c] = (c < C) ? expf(z[c] - mx) : 0.f;
-      ssum += z[c];
-    }
-    const float inv = 1.f / ssum;
+    const float ssum = softmax_exp<MAXC, float>(z, C);
     const size_t m = ((size_t)n * H * r + (size_t)ia * r + q) * Wr + (size_t)(ib0 + px) * r + pp;  // output pixel
     const int t = (int)labels[m];
     const float w = (t >= 0 && t < C) ? (weights ? weights[m] : 1.f) : 0.f;  // void rows: zero loss and gradient
-    float psum = 0.f, pt = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      z[c] *= inv;
-      psum += z[c];
-      pt = (c == t) ? z[c] : pt;
-    }
-    float inside = 1.f;
-    if (t >= 0 && t < C) {
-      float qq = pt / psum;
-      inside = dl3_clip_pass(qq);
-      qq = fminf(fmaxf(qq, 1e-7f), 1.f - 1e-7f);
-      lsum += -logf(qq) * w * inv_nnz;
-    }
-    const float gs = w * inv_nnz * inside;
+    const float gs = xent_pixel<MAXC>(z, C, ssum, t, w, inv_nnz, true, lsum);
 #pragma unroll
     for (int c = 0; c < MAXC; c++)
       if (c < C) cell[c * (rr + 1)] = (z[c] - (c == t ? 1.f : 0.f)) * gs;
@@ -324,7 +301,7 @@ __global__ __launch_bounds__(256) void count_nz_kernel(const float *__restrict__
   unsigned int c = 0;
   for (long m = (long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long)gridDim.x * 256) c += (w[m] != 0.f);
   // integer adds commute: the atomic result is order-independent (deterministic)
-  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(cnt, red[0] + red[1] + red[2] + red[3]);
@@ -389,7 +366,7 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
                                                      const float *__restrict__ nnz, float *__restrict__ probs,
                                                      float *__restrict__ dl, float *__restrict__ loss_part, long M,
                                                      int C, int Hi, int Wi, int Ho, int Wo, float sy, float sx) {
-  constexpr int MAXC = 32;
+  constexpr int MAXC = kHeadMaxC;
   __shared__ float tile[256 * MAXC];
   const float inv_nnz = 1.f / fmaxf(*nnz, DL3_NNZ_FLOOR);
   float lsum = 0.f;
@@ -399,15 +376,9 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
     const long mc = ok ? m : M - 1;
     float z[MAXC];
     if (UPSAMPLE) {
-      const int ox = (int)(mc % Wo);
-      const long q = mc / Wo;
-      const int oy = (int)(q % Ho), n = (int)(q / Ho);
-      const Lerp ly = tf1_lerp(oy, sy, Hi), lx = tf1_lerp(ox, sx, Wi);
-      const float *b = x + (size_t)n * Hi * Wi * C;
-      const float *tl = b + ((size_t)ly.lo * Wi + lx.lo) * C, *tr = b + ((size_t)ly.lo * Wi + lx.hi) * C;
-      const float *bl = b + ((size_t)ly.hi * Wi + lx.lo) * C, *br = b + ((size_t)ly.hi * Wi + lx.hi) * C;
-#pragma unroll
-      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.wl, ly.wl);  // the weight TF states
+      const PixelPos p = split_pixel(mc, Ho, Wo);
+      const BilinearTaps taps(x + (size_t)p.n * Hi * Wi * C, p.oy, p.ox, sy, sx, Hi, Wi, C);
+      taps.load<MAXC>(z, C, taps.lx.wl, taps.ly.wl);  // the weight TF states
     } else {
       // coalesced copy of the workgroup's 256 x C logits through LDS, then one row per thread (stride C is odd for
       // C = 21: conflict-free)
@@ -418,32 +389,10 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
       for (int c = 0; c < MAXC; c++) z[c] = tile[(ok ? threadIdx.x : 0) * C + min(c, C - 1)];
       __syncthreads();
     }
-    float mx = z[0];
-#pragma unroll
-    for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
-    float ssum = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      z[c] = (c < C) ? expf(z[c] - mx) : 0.f;
-      ssum += z[c];
-    }
-    const float inv = 1.f / ssum;
+    const float ssum = softmax_exp<MAXC, float>(z, C);
     const int t = (int)labels[mc];
     const float w = (t >= 0 && t < C) ? (weights ? weights[mc] : 1.f) : 0.f;  // void rows: zero loss and gradient
-    float psum = 0.f, pt = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; c++) {
-      z[c] *= inv;  // probability
-      psum += z[c];
-      pt = (c == t) ? z[c] : pt;
-    }
-    float inside = 1.f;
-    if (ok && t >= 0 && t < C) {
-      float q = pt / psum;
-      inside = dl3_clip_pass(q);
-      q = fminf(fmaxf(q, 1e-7f), 1.f - 1e-7f);
-      lsum += -logf(q) * w * inv_nnz;
-    }
+    const float gs = xent_pixel<MAXC>(z, C, ssum, t, w, inv_nnz, ok, lsum);  // z: the probabilities
     const long nrem = min((long)256, M - base) * C;
     if (probs) {
 #pragma unroll
@@ -454,7 +403,6 @@ __global__ __launch_bounds__(256) void xent32_kernel(const float *__restrict__ x
       __syncthreads();
     }
     if (dl) {
-      const float gs = w * inv_nnz * inside;
 #pragma unroll
       for (int c = 0; c < MAXC; c++)
         if (c < C) tile[threadIdx.x * C + c] = (z[c] - (c == t ? 1.f : 0.f)) * gs;
@@ -544,39 +492,13 @@ __global__ __launch_bounds__(256, 2) void xent32_fold_kernel(const float *__rest
     if (PREF && row + (int)gridDim.x < N * Ho) prefetch(row + gridDim.x);
     // one output pixel: interpolate, softmax, loss, dlogits into the LDS row (labf / wf: its label and sample weight)
     auto pixel = [&](int ox, float labf, float wf) __attribute__((always_inline)) {
-      const Lerp lx = tf1_lerp(ox, sx, Wi);
-      const float *tl = src + lx.lo * C, *tr = src + lx.hi * C;
-      const float *bl = src + (Wi + lx.lo) * C, *br = src + (Wi + lx.hi) * C;
+      const BilinearTaps taps(src, ly, ox, sx, Wi, C);
       float z[MAXC];
-#pragma unroll
-      for (int c = 0; c < MAXC; c++) z[c] = bilerp_logit(tl, tr, bl, br, c, C, lx.w, ly.w);  // the resize kernels' weight
-      float mx = z[0];
-#pragma unroll
-      for (int c = 1; c < MAXC; c++) mx = fmaxf(mx, (c < C) ? z[c] : z[0]);
-      float ssum = 0.f;
-#pragma unroll
-      for (int c = 0; c < MAXC; c++) {
-        z[c] = (c < C) ? __expf(z[c] - mx) : 0.f;
-        ssum += z[c];
-      }
-      const float inv = 1.f / ssum;
+      taps.load<MAXC>(z, C, taps.lx.w, ly.w);  // the resize kernels' weight
+      const float ssum = softmax_exp<MAXC, float, true>(z, C);
       const int t = (int)labf;
       const float w = (t >= 0 && t < C) ? wf : 0.f;  // void rows: zero loss and gradient
-      float psum = 0.f, pt = 0.f;
-#pragma unroll
-      for (int c = 0; c < MAXC; c++) {
-        z[c] *= inv;
-        psum += z[c];
-        pt = (c == t) ? z[c] : pt;
-      }
-      float inside = 1.f;
-      if (t >= 0 && t < C) {
-        float q = pt / psum;
-        inside = dl3_clip_pass(q);
-        q = fminf(fmaxf(q, 1e-7f), 1.f - 1e-7f);
-        lsum += -logf(q) * w * inv_nnz;
-      }
-      const float gs = w * inv_nnz * inside;
+      const float gs = xent_pixel<MAXC>(z, C, ssum, t, w, inv_nnz, true, lsum);
 #pragma unroll
       for (int c = 0; c < MAXC; c++)
         if (c < C) fold_tile[ox * C + c] = (z[c] - (c == t ? 1.f : 0.f)) * gs;
@@ -624,12 +546,7 @@ __global__ __launch_bounds__(256, 2) void xent32_fold_kernel(const float *__rest
   block_loss_partial(wave_sum(lsum), loss_part);
 }
 
-inline int ew_blocks(size_t n) {
-  size_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+inline int ew_blocks(size_t n) { return dl3_blocks((long)n, 256, 8192); }
 
 }  // namespace
 
@@ -721,7 +638,7 @@ extern "C" int dl3_shuffle_softmax_xent(const float *u, const float *labels, con
                                         void *stream) {
   DL3_CHECK_ARG(u && labels && nnz && du && loss_partial && N > 0 && H > 0 && W > 0 && C > 0 && r > 0,
                 "shuffle_softmax_xent: bad argument");
-  DL3_UNSUPPORTED(C > 32, "shuffle_softmax_xent: C=%d > 32 (use phase_shift + softmax_xent)", C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "shuffle_softmax_xent: C=%d > 32 (use phase_shift + softmax_xent)", C);
   const int P = dl3_shuffle_xent_partials(N, H, W, C, r);
   DL3_UNSUPPORTED(P <= 0, "shuffle_softmax_xent: a pixel of %d x %d x %d floats does not fit the LDS tile", C, r, r);
   const int PB = subpixel_tile_pixels(W, C, r, 8);
@@ -791,7 +708,7 @@ extern "C" int dl3_count_nonzero(const float *w, int M, float *out, void *stream
 extern "C" int dl3_softmax_xent(const float *logits, const float *labels, const float *weights, const float *nnz,
                                 float *probs, float *dlogits, float *loss_partial, int M, int C, void *stream) {
   DL3_CHECK_ARG(logits && labels && nnz && loss_partial && M > 0 && C > 0, "softmax_xent: bad argument");
-  if (C <= 32)
+  if (C <= kHeadMaxC)
     hipLaunchKernelGGL((xent32_kernel<false>), dim3(dl3_rows_partials(M)), dim3(256), 0, (hipStream_t)stream, logits,
                        labels, weights, nnz, probs, dlogits, loss_partial, (long)M, C, 0, 0, 0, 0, 0.f, 0.f);
   else
@@ -806,7 +723,7 @@ extern "C" int dl3_upsample_softmax_xent(const float *logits_lo, const float *la
                                          int Hi, int Wi, int Ho, int Wo, int C, void *stream) {
   DL3_CHECK_ARG(logits_lo && labels && nnz && loss_partial && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0,
                 "upsample_softmax_xent: bad argument");
-  DL3_UNSUPPORTED(C > 32, "upsample_softmax_xent: C=%d > 32 (use resize_bilinear_fwd + softmax_xent)", C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "upsample_softmax_xent: C=%d > 32 (use resize_bilinear_fwd + softmax_xent)", C);
   const long M = (long)N * Ho * Wo;
   const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
   hipLaunchKernelGGL((xent32_kernel<true>), dim3(dl3_rows_partials((int)M)), dim3(256), 0, (hipStream_t)stream,
@@ -827,7 +744,7 @@ extern "C" int dl3_upsample_softmax_xent_fold(const float *logits_lo, const floa
   DL3_CHECK_ARG(logits_lo && labels && nnz && dlogits_xfold && loss_partial && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 &&
                     Wo > 0 && C > 0,
                 "upsample_softmax_xent_fold: bad argument");
-  DL3_UNSUPPORTED(C > 32, "upsample_softmax_xent_fold: C=%d > 32", C);
+  DL3_UNSUPPORTED(C > kHeadMaxC, "upsample_softmax_xent_fold: C=%d > 32", C);
   const size_t lds = (((size_t)Wo + 2 * (size_t)Wi) * C + 2 * (size_t)Wo) * sizeof(float);
   DL3_UNSUPPORTED(lds > 64 * 1024, "upsample_softmax_xent_fold: (%d + 2*%d) x %d floats exceed 64 KB of LDS", Wo, Wi, C);
   const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;

@@ -177,6 +177,50 @@ def test_eval_tail_nullable_outputs_and_refusals():
             assert np.array_equal(a[k], b[k]), (form, k)
 
 
+@pytest.mark.parametrize("C", [5, 21])
+def test_eval_tail_bilinear_variants_agree(C):
+    """dl3_eval_tail_bilinear has a 16-byte variant (Wo % 4 == 0; labels, weights and mask 16-byte aligned: a lane owns four
+    pixels) and a scalar one.  Both interpolate the loss's logits with the weight TF states (tailmath.h, Lerp::wl), so the
+    per-pixel terms are the same floats and only the order of the 20 * 24 = 480 double additions of an image differs: at
+    most 479 * 2^-53 = 5e-14 relative, asserted as 1e-12.  At 6x8 -> 20x24 both scale factors are inexact in float32 and
+    the stated weight differs from the fused one (Lerp::w) at 11 of the 20 rows and 16 of the 24 columns; a fused weight
+    along either axis moves loss_sum by 7e-9 to 3e-8 relative (numpy emulation), four orders above the bound."""
+    import torch
+    from tests import gpu_util as GU
+    N, Hi, Wi, Ho, Wo = 2, 6, 8, 20, 24
+    rng = np.random.default_rng(7)
+    x = GU.dev(3.0 * rng.standard_normal((N, Hi, Wi, C)))
+    labels = rng.integers(0, C, N * Ho * Wo).astype(np.float32)   # all legal
+    from dl3_amd import capi
+    P = capi.lib().dl3_eval_tail_bilinear_partials(N, Hi, Wi, Ho, Wo, C)
+    assert P > 0
+    out = {}
+    for off in (0, 1):   # element offset into every per-pixel buffer: 0 -> the 16-byte variant, 1 -> the scalar one
+        lab = GU.dev(np.concatenate([np.zeros(off, np.float32), labels]))
+        wgt = GU.dev(np.ones(off + labels.size, np.float32))
+        part = torch.full((N * P,), float("nan"), dtype=torch.float64, device="cuda")
+        loss = torch.full((N,), float("nan"), dtype=torch.float64, device="cuda")
+        nnz = torch.full((N,), -1, dtype=torch.int32, device="cuda")
+        counts = torch.full((N, 3, C), -1, dtype=torch.int32, device="cuda")
+        mask = torch.full((off + N * Ho * Wo,), -1, dtype=torch.int32, device="cuda")
+        GU._KEEP.extend([part, loss, nnz, counts, mask])
+        assert (GU.ptr(lab, off) % 16 == 0) == (off == 0) and (GU.ptr(mask, off) % 16 == 0) == (off == 0)
+        GU.call("dl3_eval_tail_bilinear", GU.ptr(x), GU.ptr(lab, off), GU.ptr(wgt, off), part.data_ptr(), loss.data_ptr(),
+                nnz.data_ptr(), counts.data_ptr(), None, GU.ptr(mask, off), N, Hi, Wi, Ho, Wo, C)
+        torch.cuda.synchronize()
+        out[off] = dict(loss_sum=loss.cpu().numpy(), nnz=nnz.cpu().numpy(), counts=counts.cpu().numpy(),
+                        mask=mask.cpu().numpy()[off:])
+    a, b = out[0], out[1]
+    assert np.array_equal(a["mask"], b["mask"])
+    assert np.array_equal(a["nnz"], b["nnz"]) and np.array_equal(a["nnz"], np.full(N, Ho * Wo))
+    assert np.array_equal(a["counts"], b["counts"])
+    for n in range(N):
+        d = abs(a["loss_sum"][n] - b["loss_sum"][n]) / abs(b["loss_sum"][n])
+        print("C=%d image %d: loss_sum 16-byte %.17g scalar %.17g relative difference %.3e" % (C, n, a["loss_sum"][n],
+                                                                                             b["loss_sum"][n], d))
+        assert d <= 1e-12
+
+
 # ------------------------------------------------------------------------------------------------- engine and model
 def _model(backbone, head, classes=3, size=64, seed=1):
     import dl3_amd  # noqa: F401

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Per-kernel instruction streams of the output head's five files, one tree against another (CPU only).
+
+    tools/isa_diff.py [--rev REV] [TREE_A [TREE_B]] [-o profiles/head_refactor_isa.txt]
+
+Without trees, A is a temporary `git worktree` of REV (default HEAD: the parent of uncommitted work; pass HEAD~1 once
+the work is committed) and B is the working tree.  Each file is cross-compiled to gfx950 device assembly with the flags
+of csrc/Makefile and split per kernel.  Lines that differ between any two compiles of the same source (.file, .ident,
+the __hip_cuid_* symbol) and comments are dropped, function-local label numbers are renumbered in order of appearance,
+and the streams are compared as text: identical or different, with the instruction count, VGPRs, scratch and LDS bytes
+of both sides.  Exit status 0 whatever the verdict: the table is the result."""
+import argparse
+import concurrent.futures as cf
+import difflib
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+FILES = ["misc.hip", "evaltail.hip", "crfunary.hip", "mine.hip", "jaccard.hip"]
+CSRC = os.path.join("keras-segmentation-deeplab-v3.1_amd", "csrc")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VOLATILE = re.compile(r"^\s*\.(file|ident)\b|__hip_cuid_")
+
+
+def make_var(text, name):
+    val = os.environ.get(name) or re.search(r"^%s\s*\??=\s*(.*)$" % name, text, re.M).group(1)
+    return re.sub(r"\$\((\w+)\)", lambda r: make_var(text, r.group(1)), val).strip()
+
+
+def compile_asm(tree, fname, out):
+    mk = open(os.path.join(tree, CSRC, "Makefile")).read()
+    cmd = [make_var(mk, "HIPCC")] + make_var(mk, "CXXFLAGS").split() + ["--cuda-device-only", "-S", "-o", out, fname]
+    r = subprocess.run(cmd, cwd=os.path.join(tree, CSRC), stderr=subprocess.PIPE, text=True)
+    if r.returncode:
+        sys.exit("%s: %s failed:\n%s" % (tree, " ".join(cmd), r.stderr))
+    return open(out).read().splitlines()
+
+
+def kernels(lines):
+    """{mangled name: (stream, stats)} of every .amdhsa_kernel of one assembly file"""
+    names = [l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")]
+    out = {}
+    for name in names:
+        start = lines.index(next(l for l in lines if l.startswith(name + ":")))
+        end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+        labels, stream = {}, []
+        for l in lines[start + 1:end]:
+            l = l.split(";")[0].rstrip()
+            if not l.strip() or VOLATILE.search(l):
+                continue
+            l = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), l)
+            stream.append(l)
+        info = "\n".join(lines[end:end + 60])
+        stat = lambda key: int(re.search(r"; %s:? =? ?(\d+)" % key, info).group(1))
+        n_inst = sum(1 for l in stream if l.startswith("\t") and not l.lstrip().startswith("."))
+        out[name] = (stream, (n_inst, stat("NumVgprs"), stat("ScratchSize"), stat("LDSByteSize")))
+    return out
+
+
+def demangle(names):
+    try:
+        r = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True)
+        short = [re.sub(r"^void |\(anonymous namespace\)::", "", s).split("(")[0] for s in r.stdout.splitlines()]
+        return dict(zip(names, short))
+    except (OSError, subprocess.CalledProcessError):
+        return {n: n for n in names}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("trees", nargs="*", help="TREE_A [TREE_B]; default: a worktree of --rev, and the working tree")
+    ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("-o", "--output", default=None)
+    ap.add_argument("--diff", default=None, metavar="NAME", help="also print the unified diff of the kernels named *NAME*")
+    a = ap.parse_args()
+    tmp = tempfile.mkdtemp(prefix="isa_diff_")
+    made = None
+    if a.trees:
+        ta = os.path.abspath(a.trees[0])
+    else:
+        ta = made = os.path.join(tmp, "parent")
+        subprocess.run(["git", "-C", ROOT, "worktree", "add", "--detach", ta, a.rev], check=True, capture_output=True)
+    tb = os.path.abspath(a.trees[1]) if len(a.trees) > 1 else ROOT
+    try:
+        with cf.ThreadPoolExecutor(max_workers=min(10, os.cpu_count() or 1)) as ex:
+            jobs = {(s, f): ex.submit(compile_asm, t, f, os.path.join(tmp, "%s_%s.s" % (s, f)))
+                    for s, t in (("a", ta), ("b", tb)) for f in FILES}
+            asm = {k: kernels(j.result()) for k, j in jobs.items()}
+    finally:
+        if made:
+            subprocess.run(["git", "-C", ROOT, "worktree", "remove", "--force", made], capture_output=True)
+        shutil.rmtree(tmp, ignore_errors=True)
+    rows, n_same, n_diff = [], 0, 0
+    fmt = lambda s: "%6d %5d %7d %6d" % s if s else "%6s %5s %7s %6s" % ("-",) * 4
+    for f in FILES:
+        ka, kb = asm[("a", f)], asm[("b", f)]
+        names = list(ka) + [n for n in kb if n not in ka]
+        pretty = demangle(names)
+        for n in names:
+            sa, sb = ka.get(n), kb.get(n)
+            verdict = "only in A" if sb is None else "only in B" if sa is None else \
+                "identical" if sa[0] == sb[0] else "DIFFERENT"
+            n_same += verdict == "identical"
+            n_diff += verdict != "identical"
+            rows.append("%-12s %-44s %-9s | %s | %s" % (f, pretty[n], verdict, fmt(sa and sa[1]), fmt(sb and sb[1])))
+    head = "%-12s %-44s %-9s | %6s %5s %7s %6s | %6s %5s %7s %6s" % (
+        "file", "kernel", "stream", "A:inst", "vgpr", "scratch", "lds", "B:inst", "vgpr", "scratch", "lds")
+    text = "\n".join(["# A = %s, B = %s; gfx950" % (a.trees[0] if a.trees else a.rev,
+                                                    a.trees[1] if len(a.trees) > 1 else "the working tree"), head] + rows +
+                     ["# %d kernels: %d identical, %d not" % (len(rows), n_same, n_diff)]) + "\n"
+    sys.stdout.write(text)
+    for f in FILES:
+        for n, (sa, _) in asm[("a", f)].items():
+            sb = asm[("b", f)].get(n)
+            if a.diff and sb and sa != sb[0] and a.diff in demangle([n])[n]:
+                sys.stdout.write("\n".join(difflib.unified_diff(sa, sb[0], "A " + n, "B " + n, lineterm="", n=2)) + "\n")
+    if a.output:
+        with open(a.output, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,10 +1,13 @@
 // pwplan.h — the 1x1-convolution launch planner: which kernel a launch of csrc/pwgemm.hip takes, on which grid, and how many
 // statistic partial rows / weight-gradient slabs it writes.  Host-only C++17: no HIP type, no device call, no allocation
-// (g++ -fsyntax-only pwplan.h).  The decision exists ONCE, here: pwgemm.hip's launch_gemm / launch_wgrad switch over the
-// template instantiations a plan names and test nothing themselves, and every sizing and route query of the C ABI
-// (dl3_pwconv_partials, _route, _fwd_impl, _bwd_weight_workspace, _bwd_weight_splits) is the planner's answer for the
-// operand forms listed at the end of this file.  A route that is added or retuned in plan_gemm_one / plan_wgrad moves the
-// queries with it; the launches refuse a plan that writes more partial rows than the caller's buffer holds.
+// (g++ -fsyntax-only pwplan.h).  The decision exists ONCE, here: pwgemm.hip's launch_gemm and the family launchers of the
+// kernel files (csrc/pwargs.h) switch over the template instantiations a plan names and test nothing themselves, and every
+// sizing and route query of the C ABI (dl3_pwconv_partials, _route, _fwd_impl, _bwd_weight_workspace, _bwd_weight_splits)
+// is the planner's answer for the operand forms listed at the end of this file.  A route that is added or retuned in
+// plan_gemm_one / plan_wgrad moves the queries with it; the launches refuse a plan that writes more partial rows than the
+// caller's buffer holds.
+// EXACTLY ONE translation unit includes this header (pwgemm.hip; tests/test_host.py::test_pwplan_is_included_once): a second
+// inclusion would duplicate its per-process state, g_gemm_math and the `static` knob caches.  The kernel files take csrc/pwargs.h.
 //
 // Knobs: DL3_WS2, DL3_NARROW, DL3_COLSPLIT and DL3_WGRAD_ROW are read once per process, DL3_GEMM_CFG, DL3_GEMM_PRE,
 // DL3_GEMM_PY, DL3_WGRAD_CFG and DL3_GEMM_MATH / dl3_set_gemm_math at every call (tests set them in-process).
@@ -13,62 +16,17 @@
 #include <stdlib.h>
 
 #include "../../include/dl3.h"
+#include "pwargs.h"  // GemmArgs, WgradArgs, GemmKernel, GemmPlan, WgradPlan; DL3_STREAM_KMAX, DL3_WGRAD_MS, DL3_WS2_NW
 
-#ifndef DL3_STREAM_KMAX
-#define DL3_STREAM_KMAX 2048  // largest reduction depth the stream kernel takes (coefficient vectors in LDS)
-#endif
 #ifndef DL3_WGRAD_WGS_DEFAULT
 #define DL3_WGRAD_WGS_DEFAULT 1024
 #endif
 #ifndef DL3_GEMM_PY_DEFAULT
 #define DL3_GEMM_PY_DEFAULT 2048
 #endif
-#ifndef DL3_WGRAD_MS
-#define DL3_WGRAD_MS 16
-#endif
-#ifndef DL3_WS2_NW
-#define DL3_WS2_NW 8  // waves per workgroup of the weight-stationary MFMA kernels (pw_ws2_kernel, pw_narrowk_kernel, pw_wgrad_narrow_kernel)
-#endif
 
-namespace {  // (one translation unit includes this header; the kernels' mangled names carry the argument structs' namespace)
-
-struct GemmArgs {
-  const float *a; int lda;
-  const float *a2; int lda2;
-  const float *ka, *kb, *kc; int a_act;
-  const float *b; int ldb;
-  const float *bias;
-  float *c; int ldc;
-  int M, K, N;
-  const float *ep_x; int ld_epx;
-  const float *ep_scale, *ep_shift; int ep_act;
-  const float *ep_add; int ld_add; int add_div; float add_scale;
-  int stat_mode;  // 0 none, 1: sum c, sum c^2 ; 2: sum c, sum c*xhat
-  const float *ep_mean, *ep_invstd;
-  float *part;
-  int part_rows;  // rows the caller's partial buffer holds: the launch writes GemmPlan::rows of them and zeroes the rest itself
-  int part_ld;    // columns per partial row (0: N) — a launch over a column slice of the output (plan_gemm) writes into the whole matrix's rows
-  int mtiles;
-  const void *bp; int nsub;  // split math: weights pre-split into 3 bf16 planes in MFMA fragment order (pack_b_kernel)
-#ifdef DL3_PHASE_TIMING
-  long long *dbg;  // probe build (tools/r3/phase_probe.py): per-workgroup cycles in prologue / K loop / epilogue
-#endif
-};
-
-// weight gradient: dW[K,N] (+)= sum_m T(X)[m][k] * dY[m][n]; grid (ntn, ntk, S)
-struct WgradArgs {
-  const float *x; int ldx;
-  const float *xs, *xt; int x_act;
-  const float *g; int ldg;
-  const float *y; int ldy;
-  const float *cA, *cB, *cC;
-  float *ws;  // [S][K][N]
-  int M, K, N, Mper;
-  float *dyout; int lddy;  // nullable: dY = cA*g + cB*y + cC written out [M][N] by the workgroups of the first K-tile row
-#ifdef DL3_PHASE_TIMING
-  long long *dbg;
-#endif
-};
+namespace {  // (the planner and its state: this unit's own)
+using namespace pw;
 
 inline int pw_cdiv(int a, int b) { return (a + b - 1) / b; }
 inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
@@ -84,29 +42,6 @@ inline bool split_math() {
   return e && e[0] == 's';
 }
 
-// ---- what a launch is ------------------------------------------------------------------
-enum GemmKernel {
-  PW_LDS,          // pw_gemm_kernel<cfg>: unaligned operands or a reduction beyond DL3_STREAM_KMAX; vmode
-  PW_STREAM,       // pw_gemm_stream_kernel<cfg>: two / fwd / pre (the prefetching epilogue, cfg 4 only) / split (MATH 1)
-  PW_KSPLIT,       // pw_ksplit32_kernel<tn, two>
-  PW_WS,           // pw_fwd_ws_kernel<kq, tn>
-  PW_WS2,          // pw_ws2_kernel<kq, tn>: forward (fwd), bwd-data (!fwd; two: the 384 -> 64 form, add: with its residual)
-  PW_NARROW_FLAT,  // pw_ws2_kernel<32, 1, FLAT>: the logits layer's forward, packed output rows
-  PW_NARROWK,      // pw_narrowk_kernel<8>: the logits layer's bwd-data
-};
-struct GemmPlan {
-  int route;  // DL3_ROUTE_*
-  GemmKernel kernel;
-  int cfg;     // tiled kernels: index into kGemmCfgs
-  int kq, tn;  // the weight-stationary and K-split kernels' instantiation
-  int vmode;   // 1 = 16-byte loads on both operands, 0 = scalar loads on both (tiny GEMMs with K = number of classes), 2 = on
-               // the activation operand only (N = number of classes — the logits layer's forward)
-  bool two, fwd, pre, add, split;
-  int grid[3];
-  unsigned lds;  // dynamic LDS bytes
-  int mtiles;    // tiled kernels: row tiles the workgroups loop over
-  int rows;      // statistic partial rows the launch writes (it zeroes rows .. part_rows)
-};
 // a dl3_pwconv_fwd* / _bwd_data call: one launch, or two over disjoint column ranges of the same output (the column split)
 struct GemmLaunch {
   int n;
@@ -483,18 +418,6 @@ inline int colsum_rows(int M) {
   if (pr > 256) pr = 256;
   return pr;
 }
-
-struct WgradPlan {
-  int route;  // DL3_ROUTE_TILED, _WGRAD_ROW or _NARROW
-  int cfg;    // index into kWgCfgs (tiled and one-tile-row kernels)
-  bool narrow, row;
-  int vec;    // tiled kernel: 1 = 16-byte loads of x and of g / y, 0 = scalar loads of both, 2 = 16-byte loads of x only
-  bool split;
-  int S, Mper;  // M splits of the tiled / one-tile-row launch and rows per split
-  int grid[3];
-  int slabs;        // K x N slabs at the head of the workspace the launch writes
-  int colsum_rows;  // rows of N column sums behind them when a bias gradient is asked for
-};
 
 // two: two-tensor dY (cA given); xvec / dvec: 16-byte loads possible on x / on g and yraw; dy_out: the launch writes dY;
 // dw: the launch folds its slabs itself

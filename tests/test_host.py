@@ -713,8 +713,29 @@ def test_pwplan_header_is_host_only():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
-    hdr = os.path.join(root, "keras-segmentation-deeplab-v3.1_amd", "csrc", "pwplan.h")
-    res = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-x", "c++", hdr], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    text = open(hdr).read()
-    assert "hip/" not in text and "hipStream" not in text and "malloc" not in text.lower()
+    # ... and so does csrc/pwargs.h, the argument structs, plans and family launchers the kernel files share with it
+    for name in ("pwplan.h", "pwargs.h"):
+        hdr = os.path.join(root, "keras-segmentation-deeplab-v3.1_amd", "csrc", name)
+        res = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-x", "c++", hdr], capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr
+        text = open(hdr).read()
+        assert "hip/" not in text and "hipStream" not in text and "malloc" not in text.lower(), name
+
+
+def test_pwplan_is_included_once():
+    """csrc/pwplan.h holds per-process state (g_gemm_math, the once-per-process knob caches): exactly one file of csrc/
+    includes it, the split-math weight scratch (pack_scratch) is defined in exactly one, and the kernel files of the 1x1
+    GEMMs — every pw*.hip but pwgemm.hip, which plans, and pwfused.hip — read no environment variable: a launcher is a switch
+    over what a plan names"""
+    import glob
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "keras-segmentation-deeplab-v3.1_amd", "csrc")
+    text = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(csrc, "*")) if p.endswith((".hip", ".h", ".cpp"))}
+    assert [n for n, t in sorted(text.items()) if '#include "pwplan.h"' in t] == ["pwgemm.hip"]
+    assert [n for n, t in sorted(text.items()) if re.search(r"^[\w \*]*\bpack_scratch\(.*\) \{$", t, re.M)] == ["pwstream.hip"]
+    kernel_files = sorted(n for n in text if re.match(r"pw\w+\.hip$", n) and n not in ("pwgemm.hip", "pwfused.hip"))
+    assert kernel_files == ["pwlds.hip", "pwsmall.hip", "pwstream.hip", "pwwgrad.hip", "pwws.hip"]
+    for n in kernel_files + ["pwargs.h", "pwdev.h"]:
+        assert "getenv" not in text[n] and "env_int" not in text[n], n

@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""Per-kernel instruction streams of the output head's five files, one tree against another (CPU only).
+"""Per-kernel instruction streams of csrc/ files, one tree against another (CPU only).
 
     tools/isa_diff.py [--rev REV] [TREE_A [TREE_B]] [-o profiles/head_refactor_isa.txt]
+    tools/isa_diff.py --files-a pwgemm.hip --files-b pwgemm.hip pwstream.hip pwlds.hip ... [-o profiles/pwgemm_split_isa.txt]
 
 Without trees, A is a temporary `git worktree` of REV (default HEAD: the parent of uncommitted work; pass HEAD~1 once
 the work is committed) and B is the working tree.  Each file is cross-compiled to gfx950 device assembly with the flags
 of csrc/Makefile and split per kernel.  Lines that differ between any two compiles of the same source (.file, .ident,
 the __hip_cuid_* symbol) and comments are dropped, function-local label numbers are renumbered in order of appearance,
 and the streams are compared as text: identical or different, with the instruction count, VGPRs, scratch and LDS bytes
-of both sides.  Exit status 0 whatever the verdict: the table is the result."""
+of both sides.  Exit status 0 whatever the verdict: the table is the result.
+
+Without --files-a / --files-b the output head's five files are compared file by file.  With them (either one defaults to
+the other) the kernels of all files of a side are pooled — code that moved between files — and paired by demangled name,
+template arguments kept, `(anonymous namespace)::` and the namespace of the GEMM argument structs (`pw::`) stripped; a
+kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison."""
 import argparse
 import concurrent.futures as cf
 import difflib
@@ -46,12 +52,12 @@ def kernels(lines):
     for name in names:
         start = lines.index(next(l for l in lines if l.startswith(name + ":")))
         end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        labels, stream = {}, []
+        labels, stream, own = {}, [], name[2:] if name.startswith("_Z") else name
         for l in lines[start + 1:end]:
             l = l.split(";")[0].rstrip()
             if not l.strip() or VOLATILE.search(l):
                 continue
-            l = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), l)
+            l = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), l).replace(own, "<self>")
             stream.append(l)
         info = "\n".join(lines[end:end + 60])
         stat = lambda key: int(re.search(r"; %s:? =? ?(\d+)" % key, info).group(1))
@@ -61,21 +67,38 @@ def kernels(lines):
 
 
 def demangle(names):
+    """{mangled name: name the kernels are paired and shown by}"""
     try:
         r = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True)
-        short = [re.sub(r"^void |\(anonymous namespace\)::", "", s).split("(")[0] for s in r.stdout.splitlines()]
+        short = [re.sub(r"^void |\(anonymous namespace\)::|\bpw::", "", s).split("(")[0] for s in r.stdout.splitlines()]
         return dict(zip(names, short))
     except (OSError, subprocess.CalledProcessError):
         return {n: n for n in names}
+
+
+def pool(asm, side, files):
+    """{pairing name: (file, stream, stats)} over all files of one side"""
+    out = {}
+    for f in files:
+        pretty = demangle(list(asm[(side, f)]))
+        for n, v in asm[(side, f)].items():
+            if pretty[n] in out:
+                sys.exit("%s: two kernels named %s (%s, %s)" % (side, pretty[n], out[pretty[n]][0], f))
+            out[pretty[n]] = (f,) + v
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("trees", nargs="*", help="TREE_A [TREE_B]; default: a worktree of --rev, and the working tree")
     ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("--files-a", nargs="+", metavar="FILE", help="csrc/ files of tree A, pooled (default: those of --files-b)")
+    ap.add_argument("--files-b", nargs="+", metavar="FILE", help="csrc/ files of tree B, pooled (default: those of --files-a)")
     ap.add_argument("-o", "--output", default=None)
     ap.add_argument("--diff", default=None, metavar="NAME", help="also print the unified diff of the kernels named *NAME*")
     a = ap.parse_args()
+    # what is compared with what: the head's files one by one, or everything --files-a holds against everything --files-b holds
+    groups = [(a.files_a or a.files_b, a.files_b or a.files_a)] if a.files_a or a.files_b else [([f], [f]) for f in FILES]
     tmp = tempfile.mkdtemp(prefix="isa_diff_")
     made = None
     if a.trees:
@@ -87,7 +110,7 @@ def main():
     try:
         with cf.ThreadPoolExecutor(max_workers=min(10, os.cpu_count() or 1)) as ex:
             jobs = {(s, f): ex.submit(compile_asm, t, f, os.path.join(tmp, "%s_%s.s" % (s, f)))
-                    for s, t in (("a", ta), ("b", tb)) for f in FILES}
+                    for s, t, i in (("a", ta, 0), ("b", tb, 1)) for f in sorted({f for g in groups for f in g[i]})}
             asm = {k: kernels(j.result()) for k, j in jobs.items()}
     finally:
         if made:
@@ -95,28 +118,29 @@ def main():
         shutil.rmtree(tmp, ignore_errors=True)
     rows, n_same, n_diff = [], 0, 0
     fmt = lambda s: "%6d %5d %7d %6d" % s if s else "%6s %5s %7s %6s" % ("-",) * 4
-    for f in FILES:
-        ka, kb = asm[("a", f)], asm[("b", f)]
-        names = list(ka) + [n for n in kb if n not in ka]
-        pretty = demangle(names)
-        for n in names:
+    n_a = n_b = 0
+    diffs = []
+    for fa, fb in groups:
+        ka, kb = pool(asm, "a", fa), pool(asm, "b", fb)
+        n_a, n_b = n_a + len(ka), n_b + len(kb)
+        for n in list(ka) + [n for n in kb if n not in ka]:
             sa, sb = ka.get(n), kb.get(n)
             verdict = "only in A" if sb is None else "only in B" if sa is None else \
-                "identical" if sa[0] == sb[0] else "DIFFERENT"
+                "identical" if sa[1] == sb[1] else "DIFFERENT"
             n_same += verdict == "identical"
             n_diff += verdict != "identical"
-            rows.append("%-12s %-44s %-9s | %s | %s" % (f, pretty[n], verdict, fmt(sa and sa[1]), fmt(sb and sb[1])))
+            if verdict == "DIFFERENT":
+                diffs.append((n, sa[1], sb[1]))
+            rows.append("%-12s %-44s %-9s | %s | %s" % ((sb or sa)[0], n, verdict, fmt(sa and sa[2]), fmt(sb and sb[2])))
     head = "%-12s %-44s %-9s | %6s %5s %7s %6s | %6s %5s %7s %6s" % (
         "file", "kernel", "stream", "A:inst", "vgpr", "scratch", "lds", "B:inst", "vgpr", "scratch", "lds")
     text = "\n".join(["# A = %s, B = %s; gfx950" % (a.trees[0] if a.trees else a.rev,
                                                     a.trees[1] if len(a.trees) > 1 else "the working tree"), head] + rows +
-                     ["# %d kernels: %d identical, %d not" % (len(rows), n_same, n_diff)]) + "\n"
+                     ["# %d kernels: %d identical, %d not; A has %d, B has %d" % (len(rows), n_same, n_diff, n_a, n_b)]) + "\n"
     sys.stdout.write(text)
-    for f in FILES:
-        for n, (sa, _) in asm[("a", f)].items():
-            sb = asm[("b", f)].get(n)
-            if a.diff and sb and sa != sb[0] and a.diff in demangle([n])[n]:
-                sys.stdout.write("\n".join(difflib.unified_diff(sa, sb[0], "A " + n, "B " + n, lineterm="", n=2)) + "\n")
+    for n, sa, sb in diffs:
+        if a.diff and a.diff in n:
+            sys.stdout.write("\n".join(difflib.unified_diff(sa, sb, "A " + n, "B " + n, lineterm="", n=2)) + "\n")
     if a.output:
         with open(a.output, "w") as fh:
             fh.write(text)

@@ -43,7 +43,8 @@ KNOBS = {
     "DL3_WGRAD_ROW": ("1", "A/B", "0: the expand convolutions' weight gradient on the tiled kernel (round 6, call 18)"),
 }
 
-# headers that are one translation unit's own: their knobs are read at that unit
+# headers that are one translation unit's own: their knobs are read at that unit (csrc/pwargs.h and csrc/pwdev.h, which several
+# units include, read none: tests/test_host.py::test_pwplan_is_included_once)
 PART_OF = {"csrc/pwplan.h": "csrc/pwgemm.hip"}
 
 
@@ -74,8 +75,8 @@ def render(found):
         d, kind, what = KNOBS[name]
         sites = found[name]
         out.append("| `%s` | %s | %s | %s | %s |" % (name, d, kind, ", ".join("`%s`" % s for s in sites[:3]) + (" …" if len(sites) > 3 else ""), what))
-    out += ["", "Build-time macros of `csrc/` (probe builds under `build_variants/`, never the shipped library): `DL3_PHASE_TIMING`,",
-            "`DL3_STREAM_KT_FWD`, `DL3_STREAM_KT_BWD1`, `DL3_STREAM_PD_SMALL`, `DL3_WGRAD_MS`, `DL3_WS2_NW`, `DL3_WS2_DIRECT_EPILOGUE`,",
+    out += ["", "Build-time macros of `csrc/` (probe builds under `build_variants/`, never the shipped library): `DL3_STREAM_KMAX`,",
+            "`DL3_STREAM_KT_FWD`, `DL3_STREAM_KT_BWD1`, `DL3_STREAM_PD_SMALL`, `DL3_WGRAD_MS`, `DL3_WS2_NW`, `DL3_WS2_XPRE_TN`,",
             "`DL3_DBG_NOSTORE`, `DL3_DBG_NOSTAT`, `DL3_EPI_NOFENCE`, `DL3_ACT_MINMAX`.", ""]
     return "\n".join(out)
 

@@ -833,6 +833,8 @@ class Engine:
         N_, H, W, C = v.shape
         if v.off != 0 or v.ld != C:
             raise NotImplementedError("depthwise conv on a channel slice (%s)" % l.name)
+        if C % 4:   # (dw_check in csrc/dwconv.hip refuses it at the first launch: say so while lowering)
+            raise NotImplementedError("depthwise conv over %d channels (%s): the kernels take multiples of 4" % (C, l.name))
         s, r = l.cfg["stride"], l.cfg["rate"]
         if l.cfg["padding"] == "same":
             Ho, pt = _same_pads(H, 3, s, r)
@@ -1704,6 +1706,10 @@ class GradSink:
         self.stat = last and bool(buf.bns)
         if self.stat and not whole:
             raise NotImplementedError("BN-backward statistics through a channel slice")
+        if not whole and add is not gout:
+            # this launch would write ONE slice of a gradient buffer nobody has written yet, and the next contribution
+            # takes the whole buffer as its addend: the other slices would be read before anything was stored in them
+            raise NotImplementedError("first gradient contribution into a channel slice of a shared buffer")
         self.out = gout.data_ptr() + 4 * off
         self.add = None if add is None else add.data_ptr() + 4 * off
         if inv.act != ACT_NONE:

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import dl3_oracle as O
+from tests import graph_ref
 from tests.gpu_util import dropout_keep_mask, relerr
 
 pytestmark = pytest.mark.gpu
@@ -713,9 +714,8 @@ def test_learns_a_toy_segmentation_task():
 def test_subpixel_with_kernel_size_above_one(k, padding):
     """Subpixel IS a Conv2D with any kernel_size (subpixel.py:42-58; icnr_weights' default shape is 3x3, :9): round 2
     silently lowered kernel_size != 1 as a 1x1 GEMM.  Forward, loss and every gradient of a small graph
-    conv3x3/s2 -> BN -> relu -> Subpixel(3, k, r=2) -> softmax against a float64 torch-autograd restatement written
-    here (TF SAME padding, the reference's own phase shift, Keras weighted cross-entropy)."""
-    import torch.nn.functional as F
+    conv3x3/s2 -> BN -> relu -> Subpixel(3, k, r=2) -> softmax against the float64 torch-autograd graph walk of
+    tests/graph_ref.py (TF SAME padding, the reference's own phase shift, Keras weighted cross-entropy)."""
     import dl3_amd  # noqa: F401
     from dl3_amd import graph as G
     from dl3_amd.subpixel import Subpixel, icnr_weights
@@ -743,35 +743,15 @@ def test_subpixel_with_kernel_size_above_one(k, padding):
     eng.set_targets(labels, sw)
     eng.fwd_bwd()
     torch.cuda.synchronize()
-    # ---- float64 restatement
-    P = {n: torch.tensor(np.asarray(w, np.float64), requires_grad=True) for l in model.layers for n, w in l.weights.items()
-         if "/moving_" not in n}
-    xt = torch.tensor(xin.astype(np.float64)).permute(0, 3, 1, 2)
-    a = F.conv2d(F.pad(xt, (0, 1, 0, 1)), P["c0/kernel:0"].permute(3, 2, 0, 1), stride=2)  # SAME, even size: pad at the end
-    mu, var = a.mean((0, 2, 3), keepdim=True), a.var((0, 2, 3), unbiased=False, keepdim=True)
-    a = (a - mu) / torch.sqrt(var + 1e-3) * P["c0_BN/gamma:0"].view(1, -1, 1, 1) + P["c0_BN/beta:0"].view(1, -1, 1, 1)
-    a = torch.relu(a)
-    if padding == "same":
-        a = F.pad(a, ((k - 1) // 2, k - 1 - (k - 1) // 2) * 2)
-    y = F.conv2d(a, P["sp/kernel:0"].permute(3, 2, 0, 1)) + P["sp/bias:0"].view(1, -1, 1, 1)
-    y = y.permute(0, 2, 3, 1)                                             # [N, a, b, C*r*r]
-    Nn, Ha, Wb, _ = y.shape
-    # out[n, ia*r+q, ib*r+p, ch] = I[n, ia, ib, ch*r*r + p*r + q]  (subpixel.py:77-88)
-    y = y.reshape(Nn, Ha, Wb, classes, r, r).permute(0, 1, 5, 2, 4, 3).reshape(Nn, Ha * r, Wb * r, classes)
-    assert (Ha * r, Wb * r) == (Hs, Ws)
-    logits = y.reshape(Nn, Hs * Ws, classes)
-    t = torch.tensor(labels.astype(np.int64))
-    w = torch.tensor(sw.astype(np.float64))
-    p = torch.softmax(logits, -1)
-    pt = torch.gather(p, 2, t.clamp(max=classes - 1).unsqueeze(-1)).squeeze(-1).clamp(1e-7, 1 - 1e-7)
-    ell = torch.where(t < classes, -torch.log(pt), torch.zeros_like(pt))
-    loss = (ell * w).sum() / (w != 0).sum()
-    loss.backward()
+    # ---- float64 reference: the graph walk (TF SAME padding, the reference's own phase shift, Keras weighted cross-entropy)
+    ref = graph_ref.run(model, xin, labels, sw, dtype=torch.float64)
+    Nn, logits, loss = B, ref.logits.reshape(B, Hs * Ws, classes), ref.loss
+    assert sorted(ref.grads) == ["c0/kernel:0", "c0_BN/beta:0", "c0_BN/gamma:0", "sp/bias:0", "sp/kernel:0"]
     got = eng.logits().reshape(Nn, Hs * Ws, classes)
-    assert relerr(got, logits.detach().numpy()) < 1e-4
+    assert relerr(got, logits) < 1e-4
     assert abs(float(eng.loss[0].item()) - float(loss)) < 1e-5 * abs(float(loss))
-    for n, pt_ in P.items():
-        e = _l2(eng.grad_of(n), pt_.grad.numpy())
+    for n, g in ref.grads.items():
+        e = _l2(eng.grad_of(n), g)
         print("   %-16s grad rel-L2 %.2e" % (n, e))
         assert e < 2e-4, (n, e)
 
@@ -780,8 +760,8 @@ def test_activation_without_batchnorm_into_the_logits_layer():
     """Input -> Conv2D(256, 1) -> Activation("relu") -> Conv2D(21, 1) -> softmax at B = 2 (131 072 rows): the logits
     convolution reads a view with an activation and no BatchNorm (scale and shift NULL), and its weight gradient takes
     pw_wgrad_narrow_kernel (tests/test_host.py asserts the plan), which used to rectify x only when a scale came with the
-    activation — the graph trained on the gradient of the unrectified input.  Logits, loss and every gradient against a
-    float64 torch-autograd restatement written here."""
+    activation — the graph trained on the gradient of the unrectified input.  Logits, loss and every gradient against the
+    float64 torch-autograd graph walk of tests/graph_ref.py."""
     import dl3_amd  # noqa: F401
     from dl3_amd import graph as G
     from tests.test_host import _act_only_logits_model
@@ -801,24 +781,15 @@ def test_activation_without_batchnorm_into_the_logits_layer():
     eng.set_targets(labels, sw)
     eng.fwd_bwd()
     torch.cuda.synchronize()
-    # ---- float64 restatement
-    P = {n: torch.tensor(np.asarray(w, np.float64), requires_grad=True) for l in model.layers for n, w in l.weights.items()}
-    xt = torch.tensor(xin.astype(np.float64)).reshape(B * H * W, cin)
-    a = torch.relu(xt @ P["c0/kernel:0"].reshape(cin, 256) + P["c0/bias:0"])
-    logits = (a @ P["logits/kernel:0"].reshape(256, classes) + P["logits/bias:0"]).reshape(B, H * W, classes)
-    t = torch.tensor(labels.astype(np.int64))
-    w = torch.tensor(sw.astype(np.float64))
-    p = torch.softmax(logits, -1)
-    pt = torch.gather(p, 2, t.clamp(max=classes - 1).unsqueeze(-1)).squeeze(-1).clamp(1e-7, 1 - 1e-7)
-    ell = torch.where(t < classes, -torch.log(pt), torch.zeros_like(pt))
-    loss = (ell * w).sum() / (w != 0).sum()
-    loss.backward()
+    # ---- float64 reference: the graph walk
+    ref = graph_ref.run(model, xin, labels, sw, dtype=torch.float64)
+    logits, loss = ref.logits.reshape(B, H * W, classes), ref.loss
     got = eng.logits().reshape(B, H * W, classes)
-    assert _l2(got, logits.detach().numpy()) < 2e-4
+    assert _l2(got, logits) < 2e-4
     assert abs(float(eng.loss[0].item()) - float(loss)) < 1e-5 * abs(float(loss))
-    assert sorted(P) == ["c0/bias:0", "c0/kernel:0", "logits/bias:0", "logits/kernel:0"]
-    for n, pt_ in P.items():
-        e = _l2(eng.grad_of(n), pt_.grad.numpy())
+    assert sorted(ref.grads) == ["c0/bias:0", "c0/kernel:0", "logits/bias:0", "logits/kernel:0"]
+    for n, g in ref.grads.items():
+        e = _l2(eng.grad_of(n), g)
         print("   %-16s grad rel-L2 %.2e" % (n, e))
         assert e < 2e-4, (n, e)
 

@@ -55,6 +55,36 @@ def argmax_rows(t, M, C):
     return out
 
 
+_ARG_NAMES = {}
+
+
+def arg_names(name):
+    """the parameter names include/dl3.h gives entry point `name`, in order, without the trailing stream (parsed once
+    per entry point)"""
+    if name not in _ARG_NAMES:
+        _ARG_NAMES[name] = tuple(a for _, a in capi.protos()[name][1][:-1])
+    return _ARG_NAMES[name]
+
+
+class Launch(tuple):
+    """One recorded launch: (name, fn, args, ws_index).  args is the mutable list of the call's arguments in the header's
+    order (the replay appends the stream); ws_index is the position of the scratch pointer the engine patches in once
+    the scratch is sized, or None.  Arguments are read and patched by the names include/dl3.h gives them."""
+    __slots__ = ()
+
+    def _at(self, key):
+        names = arg_names(self[0])
+        if key not in names:
+            raise ValueError("%s has no parameter %r; include/dl3.h names %s" % (self[0], key, ", ".join(names)))
+        return names.index(key)
+
+    def arg(self, key):
+        return self[2][self._at(key)]
+
+    def set(self, key, value):
+        self[2][self._at(key)] = value
+
+
 class Plan:
     """One launch sequence of an engine under the capture rule all of its plans share: the first counted run() calls
     `body` eagerly (module loading, allocator warm-up), the second captures it as one hipGraph and replays that, every
@@ -322,7 +352,7 @@ class Engine:
         self._side_stream = None
         self._fork_events = []
         self.side_scratch_bytes = 0
-        self._side_scratch_users = []
+        self._scratch_users, self._side_scratch_users = [], []   # launches whose `workspace` is the shared scratch
         self.units = []
         self.views = {}
         self.bufs = []
@@ -344,12 +374,12 @@ class Engine:
             if self.mining:
                 self.op(self.ops_bwd, "dl3_counter_add", self.mine_step.data_ptr(), 1)
         self.scratch = self.empty(max(self.scratch_bytes // 4, 4))
-        for op in self._scratch_users:
-            op[2][op[3]] = self.scratch.data_ptr()
+        for rec in self._scratch_users:
+            rec.set("workspace", self.scratch.data_ptr())
         if self._side_scratch_users:  # the side stream's launches are ordered among themselves: one workspace of their own
             self.side_scratch = self.empty(max(self.side_scratch_bytes // 4, 4))
-            for op in self._side_scratch_users:
-                op[2][op[3]] = self.side_scratch.data_ptr()
+            for rec in self._side_scratch_users:
+                rec.set("workspace", self.side_scratch.data_ptr())
         self.dirty = True
 
     # ------------------------------------------------------------------ memory
@@ -471,17 +501,26 @@ class Engine:
             l._engine = self
 
     # ------------------------------------------------------------------ op recording
-    def op(self, lst, name, *args):
-        fn = getattr(self.lib, name)
-        rec = (name, fn, list(args), None)
+    def op(self, lst, name, *args, ws=None, side=False):
+        """record the launch name(*args, stream) at the end of lst.  The argument count is checked against include/dl3.h
+        here, while lowering.  side: the launch may leave the backward chain (see self.fork).  ws=nbytes: it takes the
+        shared scratch — the side stream's where it goes there — through the parameter the header calls `workspace`
+        (the call site passes 0 there; the pointer is patched in once the scratch's size is known)"""
+        names = arg_names(name)
+        if len(args) != len(names):
+            raise TypeError("%s takes %d arguments in front of the stream (include/dl3.h), %d were recorded"
+                            % (name, len(names), len(args)))
+        side = side and self.fork
+        rec = Launch((name, getattr(self.lib, name), list(args), None if ws is None else names.index("workspace")))
         lst.append(rec)
-        return rec
-
-    def op_side(self, lst, name, *args):
-        """op for a launch that may leave the backward chain (see self.fork) and brings its own workspace"""
-        rec = self.op(lst, name, *args)
-        if self.fork:
+        if side:
             self._side.add(id(rec))
+        if ws is not None and side:
+            self.side_scratch_bytes = max(self.side_scratch_bytes, int(ws))
+            self._side_scratch_users.append(rec)
+        elif ws is not None:
+            self.scratch_bytes = max(self.scratch_bytes, int(ws))
+            self._scratch_users.append(rec)
         return rec
 
     def defer_fold(self, P, n):
@@ -493,28 +532,6 @@ class Engine:
             self._folds.append((int(src_ptr), int(dst_ptr), int(P), int(n)))
         else:
             self.op(self.ops_bwd, "dl3_reduce_partials", src_ptr, P, n, dst_ptr)
-
-    _scratch_users = None
-
-    def op_ws(self, lst, name, nbytes, ws_index, *args):
-        """op that needs the shared scratch workspace (pointer patched in once its size is known)"""
-        self.scratch_bytes = max(self.scratch_bytes, int(nbytes))
-        args = list(args)
-        rec = (name, getattr(self.lib, name), args, ws_index)
-        lst.append(rec)
-        self._scratch_users.append(rec)
-        return rec
-
-    def op_ws_side(self, lst, name, nbytes, ws_index, *args):
-        """op_ws for a launch that may leave the backward chain (see self.fork): its workspace is the side stream's"""
-        if not self.fork:
-            return self.op_ws(lst, name, nbytes, ws_index, *args)
-        self.side_scratch_bytes = max(self.side_scratch_bytes, int(nbytes))
-        rec = (name, getattr(self.lib, name), list(args), ws_index)
-        lst.append(rec)
-        self._side_scratch_users.append(rec)
-        self._side.add(id(rec))
-        return rec
 
     def run_ops_forked(self, lst):
         """lst with the launches marked in self._side on a second stream: each one waits for the event recorded on the
@@ -562,7 +579,6 @@ class Engine:
 
     # ------------------------------------------------------------------ forward lowering
     def _lower(self):
-        self._scratch_users = []
         m = self.model
         topo = m._topo
         self.consumers = {}
@@ -1131,9 +1147,7 @@ class Engine:
                 t0 += tx * ((r + 31) // 32)
             self._tdesc = torch.tensor(rows, dtype=torch.int64, device=self.device)
             self._keep.append(self._tdesc)
-            rec = ("dl3_transpose_batched", getattr(self.lib, "dl3_transpose_batched"),
-                   [self._tdesc.data_ptr(), len(rows), t0], None)
-            self.ops_bwd.insert(first_bwd, rec)
+            self.ops_bwd.insert(first_bwd, self.op([], "dl3_transpose_batched", self._tdesc.data_ptr(), len(rows), t0))
         if self._folds:
             # (the slabs were written by launches on either stream: the fold sits behind the join at the end of the list)
             rows, b0 = [], 0
@@ -1163,13 +1177,12 @@ class Engine:
         dy = ptr(self.dy_buf)
         pending = None
         for rec in self.ops_bwd:
-            name, args = rec[0], rec[2]
-            if name == "dl3_pwconv_bwd_weight_dy":
+            if rec[0] == "dl3_pwconv_bwd_weight_dy":
                 assert pending is None, "two dY writers without the first one's reader in between"
-                assert args[-2] == dy and id(rec) not in self._side, "dY written off the main stream / into another buffer"
-                pending = (args[14], args[15], args[16])    # M, K, N
-            elif name == "dl3_pwconv_bwd_data" and args[0] == dy:
-                assert pending == (args[22], args[23], args[24]), ("bwd-data reads a dY another layer wrote", pending)
+                assert rec.arg("dy_out") == dy and id(rec) not in self._side, "dY written off the main stream / into another buffer"
+                pending = [rec.arg(k) for k in "MKN"]
+            elif rec[0] == "dl3_pwconv_bwd_data" and rec.arg("g") == dy:
+                assert pending == [rec.arg(k) for k in "MKN"], ("bwd-data reads a dY another layer wrote", pending)
                 pending = None
         assert pending is None, "a materialised dY was never read"
 
@@ -1816,8 +1829,8 @@ class PwUnit(_ConvBase):
         iu = getattr(self, "img_unit", None)
         if iu is not None and iu.fwd_rec[0] == "dl3_pwconv_fwd_rows":
             rec = iu.fwd_rec
-        assert rec[0] in ("dl3_pwconv_fwd", "dl3_pwconv_fwd_add", "dl3_pwconv_fwd_rows") and rec[2][6] is None and self.bias is None
-        rec[2][6] = neg_offset_ptr
+        assert rec[0] in ("dl3_pwconv_fwd", "dl3_pwconv_fwd_add", "dl3_pwconv_fwd_rows") and rec.arg("bias") is None and self.bias is None
+        rec.set("bias", neg_offset_ptr)
         self.outv.buf.centred.add(self.outv.off)
 
     def _bwd_img_add(self, g, ldg, y, ldy, cA, cB, cC):
@@ -1910,13 +1923,13 @@ class PwUnit(_ConvBase):
                 # the launch leaves its [S][K][N] slabs in a workspace of its own; folded at the end of the pass
                 own = eng.empty(ws // 4 + 4)
                 eng.own_fold_ws_bytes += ws + 16
-                eng.op_side(eng.ops_bwd, fn, inv.p(), inv.ld, s, t, a, g, ldg, y, ldy, cA, cB, cC,
-                            None, None, M, K, N, ptr(own), ws, *tail)
+                eng.op(eng.ops_bwd, fn, inv.p(), inv.ld, s, t, a, g, ldg, y, ldy, cA, cB, cC,
+                       None, None, M, K, N, ptr(own), ws, *tail, side=True)
                 eng.fold(ptr(own), S, K * N, eng.gptr(self.wname()) + 4 * self.wrow0 * N)
             else:
-                eng.op_ws_side(eng.ops_bwd, fn, ws, 17, inv.p(), inv.ld, s, t, a, g, ldg, y, ldy, cA, cB,
-                               cC, eng.gptr(self.wname()) + (4 * self.wrow0 * N if eng.trainable(self.wname()) else 0),
-                               eng.gptr(self.bias) if self.bias else None, M, K, N, 0, ws, *tail)
+                eng.op(eng.ops_bwd, fn, inv.p(), inv.ld, s, t, a, g, ldg, y, ldy, cA, cB, cC,
+                       eng.gptr(self.wname()) + (4 * self.wrow0 * N if eng.trainable(self.wname()) else 0),
+                       eng.gptr(self.bias) if self.bias else None, M, K, N, 0, ws, *tail, ws=ws, side=True)
         if dy:
             # from here on the layer's gradient operand is the one tensor the weight-gradient launch just wrote
             g, ldg, y, ldy, cA, cB, cC = dy, N, None, 0, None, None, None
@@ -2012,8 +2025,8 @@ class Conv3Unit(_ConvBase):
         s, t, a = inv.xform()
         if eng.trainable(self.wname()):
             ws = eng.lib.dl3_conv3x3_mfma_bwd_weight_workspace(*self.geom[:6], Ho, Wo)
-            eng.op_ws(eng.ops_bwd, "dl3_conv3x3_mfma_bwd_weight", ws, 20, inv.p(), s, t, a, g, y, cA, cB, cC,
-                      eng.gptr(self.wname()), *self.geom, 0, ws)
+            eng.op(eng.ops_bwd, "dl3_conv3x3_mfma_bwd_weight", inv.p(), s, t, a, g, y, cA, cB, cC,
+                   eng.gptr(self.wname()), *self.geom, 0, ws, ws=ws)
         ibuf = inv.buf
         if not ibuf.requires_grad:
             return
@@ -2129,15 +2142,15 @@ class ResizeUnit:
         elif plain:
             gout, add, last = eng.contrib_kernel(ibuf)
             ws = eng.lib.dl3_resize_bilinear_bwd_workspace(B, Hi, Wi, Ho, Wo, C)
-            eng.op_ws(eng.ops_bwd, "dl3_resize_bilinear_bwd", ws, 11, g, outv.ld, ptr(gout), ibuf.ld, B, Hi, Wi, Ho, Wo,
-                      C, 1 if add is not None else 0, 0, ws)
+            eng.op(eng.ops_bwd, "dl3_resize_bilinear_bwd", g, outv.ld, ptr(gout), ibuf.ld, B, Hi, Wi, Ho, Wo,
+                   C, 1 if add is not None else 0, 0, ws, ws=ws)
             if add is not None and add is not gout:
                 raise NotImplementedError("resize backward with a foreign addend")
         else:
             tmp = eng.empty(ibuf.M * C)
             ws = eng.lib.dl3_resize_bilinear_bwd_workspace(B, Hi, Wi, Ho, Wo, C)
-            eng.op_ws(eng.ops_bwd, "dl3_resize_bilinear_bwd", ws, 11, g, outv.ld, ptr(tmp), C, B, Hi, Wi, Ho, Wo, C, 0,
-                      0, ws)
+            eng.op(eng.ops_bwd, "dl3_resize_bilinear_bwd", g, outv.ld, ptr(tmp), C, B, Hi, Wi, Ho, Wo, C, 0,
+                   0, ws, ws=ws)
             eng.contrib_elementwise(ibuf, inv, ptr(tmp), C)
 
 

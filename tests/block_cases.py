@@ -314,7 +314,12 @@ def refuse_foreign_addend(G, shape):
 
 # ---------------------------------------------------------------------------------------------------- predicates
 def ops(lst, name):
-    return [rec[2] for rec in lst if rec[0] == name]
+    """the records of entry point `name`: their arguments are read by the header's names (engine.Launch.arg)"""
+    return [rec for rec in lst if rec[0] == name]
+
+
+def vals(rec, *keys):
+    return [rec.arg(k) for k in keys]
 
 
 def names(lst):
@@ -329,24 +334,22 @@ def _ptr(t):
     return t.data_ptr()
 
 
-# argument positions (engine.py): dl3_pwconv_bwd_data(g0 ldg1 y2 ldy3 cA4 cB5 cC6 wT7 out8 ld9 x10 ldx11 scale12 shift13
-# act14 add15 ld16 .. mean19 invstd20 dpart21 M22 K23 N24); dl3_pwconv_bwd_fused(x0 .. g5 ldg6 y7 ldy8 cA9 cB10 cC11 wT12 -
-# out14 ld15 add16 ld17 sx18 sld19 mean20 invstd21 dpart22 M23 K24 N25)
 def p_zeropad(e):
     d = ops(e.ops_fwd, "dl3_dwconv3x3_fwd")
-    # geom behind the six leading arguments: B H W C stride rate pt pl Ho Wo
-    return len(d) == 1 and d[0][10:14] == [2, 1, 1, 1] and "dl3_dwconv3x3_bwd" in names(e.ops_bwd)
+    return (len(d) == 1 and vals(d[0], "stride", "rate", "pad_t", "pad_l") == [2, 1, 1, 1]
+            and "dl3_dwconv3x3_bwd" in names(e.ops_bwd))
 
 
 def p_dy_on(e):
     wd, bd = ops(e.ops_bwd, "dl3_pwconv_bwd_weight_dy"), ops(e.ops_bwd, "dl3_pwconv_bwd_data")
     dy = e.dy_buf is not None and _ptr(e.dy_buf)
-    return bool(wd) and any(a[0] == dy and a[2] is None and a[4] is None for a in bd)
+    return bool(wd) and any(a.arg("g") == dy and a.arg("yraw") is None and a.arg("cA") is None for a in bd)
 
 
 def p_dy_off(e):
     bd = ops(e.ops_bwd, "dl3_pwconv_bwd_data")
-    return e.dy_buf is None and not ops(e.ops_bwd, "dl3_pwconv_bwd_weight_dy") and sum(a[4] is not None for a in bd) >= 2
+    return (e.dy_buf is None and not ops(e.ops_bwd, "dl3_pwconv_bwd_weight_dy")
+            and sum(a.arg("cA") is not None for a in bd) >= 2)
 
 
 def _adds(e):
@@ -361,34 +364,35 @@ def p_residual(e):
     for u in _adds(e):
         g = u.outv.buf.grad
         ok = ok and u.b.buf.grad is g and u.a.buf.grad is not g
-        taken = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data") + [f[:8] + [f[14]] + [0] * 6 + [f[16]] for f in
-                                                                        ops(e.ops_bwd, "dl3_pwconv_bwd_fused")]
-                 if a[8] == _ptr(u.a.buf.grad) and a[15] == _ptr(g)]
+        # (dl3_pwconv_bwd_data and dl3_pwconv_bwd_fused share the names of the gradient they write and its addend)
+        taken = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data") + ops(e.ops_bwd, "dl3_pwconv_bwd_fused")
+                 if a.arg("dx") == _ptr(u.a.buf.grad) and a.arg("dx_add") == _ptr(g)]
         ok = ok and len(taken) == 1
-        early = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data") if a[8] == _ptr(g) and a[19] == u.b.buf.vptr(2)
-                 and a[10] == _ptr(u.b.buf.t)]
-        early += [f for f in ops(e.ops_bwd, "dl3_pwconv_bwd_fused") if f[14] == _ptr(g) and f[20] == u.b.buf.vptr(2)
-                  and f[18] == _ptr(u.b.buf.t)]
+        early = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data")
+                 if vals(a, "dx", "x_mean", "x") == [_ptr(g), u.b.buf.vptr(2), _ptr(u.b.buf.t)]]
+        early += [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_fused")
+                  if vals(a, "dx", "x_mean", "stat_x") == [_ptr(g), u.b.buf.vptr(2), _ptr(u.b.buf.t)]]
         ok = ok and len(early) == 1
     return ok and bool(_adds(e))
 
 
 def p_stacked(e):
-    a = _adds(e)
-    return len(a) == 2 and a[1].a.buf is a[0].outv.buf and not a[0].outv.buf.bns and p_residual(e)
+    adds = _adds(e)
+    return len(adds) == 2 and adds[1].a.buf is adds[0].outv.buf and not adds[0].outv.buf.bns and p_residual(e)
 
 
 def p_fused(e):
     f = ops(e.ops_bwd, "dl3_pwconv_bwd_fused")
-    own = lambda a: a[18] == a[0]   # noqa: E731  (sums against the forward input itself)
-    return (p_residual(e) and any(a[16] is not None for a in f) and any(a[20] is not None and not own(a) for a in f)
-            and len(f) >= 3)
+    own = lambda a: a.arg("stat_x") == a.arg("x")   # noqa: E731  (sums against the forward input itself)
+    return (p_residual(e) and any(a.arg("dx_add") is not None for a in f)
+            and any(a.arg("x_mean") is not None and not own(a) for a in f) and len(f) >= 3)
 
 
 def p_fused_sup1(e):
-    f = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_fused") if a[24] > 64]
-    return (len(f) == 1 and e.lib.dl3_pwconv_bwd_fused_supported(*f[0][23:26]) == 1 and f[0][16] is None
-            and (f[0][20] is None or f[0][18] == f[0][0]))
+    wide = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_fused") if a.arg("K") > 64]
+    return len(wide) == 1 and all(
+        e.lib.dl3_pwconv_bwd_fused_supported(*vals(a, "M", "K", "N")) == 1 and a.arg("dx_add") is None
+        and (a.arg("x_mean") is None or a.arg("stat_x") == a.arg("x")) for a in wide)
 
 
 def p_fork(e):
@@ -400,21 +404,21 @@ def p_fork(e):
 def p_subsample(e):
     n = names(e.ops_bwd)
     i = n.index("dl3_subsample_bwd") if "dl3_subsample_bwd" in n else -1
-    d = [a[10:12] for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd")]
-    acts = [a[3] for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd")]
+    d = [vals(a, "stride", "rate") for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd")]
+    acts = [a.arg("in_act") for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd")]
     return ("dl3_subsample_fwd" in names(e.ops_fwd) and i >= 0 and n[i + 1] == "dl3_grad_finish" and [2, 1] in d
             and acts == [1, 0, 1])   # relu of a rectified view, none in front of depth_activation, the leading relu
 
 
 def p_dw_sx(e):
     sx = ops(e.ops_bwd, "dl3_dwconv3x3_bwd_sx")
-    return len(sx) == 1 and sx[0][13] is not None and "dl3_grad_finish" not in names(e.ops_bwd) and len(_adds(e)) == 2
+    return len(sx) == 1 and sx[0].arg("x_mean") is not None and "dl3_grad_finish" not in names(e.ops_bwd) and len(_adds(e)) == 2
 
 
 def p_dw_gather(e):
     n = names(e.ops_bwd)
     return "dl3_dwconv3x3_bwd_sx" not in n and n.count("dl3_grad_finish") >= 1 and all(
-        a[-1] == 1 for a in ops(e.ops_bwd, "dl3_dwconv3x3_bwd"))
+        a.arg("impl") == 1 for a in ops(e.ops_bwd, "dl3_dwconv3x3_bwd"))
 
 
 def _cat(e, name="cat"):
@@ -435,16 +439,17 @@ def p_aspp_split(mode=None):
               and f.count("dl3_bn_finalize_direct") >= 5
               and [o for _, o, _ in cat.bns] == [0, cat.ld // 3, 2 * cat.ld // 3]
               # the second rows GEMM reads kernel row 0, the per-pixel GEMM the rows behind the pooled branch's
-              and add[0][5] - rows[1][5] == 4 * rows[1][10] * rows[1][11])
-        big = [a for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd") if a[8] < a[11] < a[7] <= a[11] + 2]   # W < rate < H <= rate + 2
+              and add[0].arg("w") - rows[1].arg("w") == 4 * rows[1].arg("K") * rows[1].arg("N"))
+        big = [a for a in ops(e.ops_fwd, "dl3_dwconv3x3_fwd") if a.arg("W") < a.arg("rate") < a.arg("H") <= a.arg("rate") + 2]
         ok = ok and len(big) == 1
         dy = e.dy_buf is not None and _ptr(e.dy_buf)
+        scales = [a.arg("in_scale") for a in gaps]
         if mode == "bn":    # sum(cA*g + cC), sum(cB*y), their sum
-            return ok and len(gaps) == 2 and gaps[0][2] is not None and gaps[1][2] is not None and "dl3_affine_add" in b
+            return ok and len(gaps) == 2 and scales[0] is not None and scales[1] is not None and "dl3_affine_add" in b
         if mode == "dy":
-            return ok and len(gaps) == 1 and gaps[0][2] is None and gaps[0][0] == dy
+            return ok and len(gaps) == 1 and scales[0] is None and gaps[0].arg("x") == dy
         if mode == "plain":
-            return ok and len(gaps) == 1 and gaps[0][2] is None and gaps[0][0] != dy and not cat_consumer_has_bn(e)
+            return ok and len(gaps) == 1 and scales[0] is None and gaps[0].arg("x") != dy and not cat_consumer_has_bn(e)
         return ok
     return pred
 
@@ -455,7 +460,8 @@ def cat_consumer_has_bn(e):
 
 def p_aspp_dropout(e):
     gf = ops(e.ops_bwd, "dl3_grad_finish")
-    return p_aspp_split("dy")(e) and any(a[18] > 0 for a in gf) and any(a[15] > 0 for a in ops(e.ops_fwd, "dl3_affine_add"))
+    return (p_aspp_split("dy")(e) and any(a.arg("drop_rate") > 0 for a in gf)
+            and any(a.arg("drop_seed") > 0 for a in ops(e.ops_fwd, "dl3_affine_add")))
 
 
 def p_aspp_materialised(e):
@@ -463,7 +469,8 @@ def p_aspp_materialised(e):
     rz = ops(e.ops_fwd, "dl3_resize_bilinear_fwd")
     b = names(e.ops_bwd)
     i = b.index("dl3_gap_fwd") if "dl3_gap_fwd" in b else -1
-    return (id(cat) not in e.bcast_src and len(rz) == 1 and rz[0][8:10] == [1, 1] and rz[0][5] == cat.t.data_ptr() + 4 * 48
+    return (id(cat) not in e.bcast_src and len(rz) == 1 and vals(rz[0], "Hi", "Wi") == [1, 1]
+            and rz[0].arg("y") == cat.t.data_ptr() + 4 * 48
             and "dl3_resize_bilinear_bwd" not in b and i >= 0 and b[i + 1] == "dl3_grad_finish"
             and "dl3_pwconv_fwd_add" not in names(e.ops_fwd))
 
@@ -473,18 +480,19 @@ def p_decoder(swap, plain, twice=False):
         cat = _cat(e, "dec_cat")
         rz = ops(e.ops_fwd, "dl3_resize_bilinear_fwd")
         rb = ops(e.ops_bwd, "dl3_resize_bilinear_bwd")
-        off = rz[0][5] - _ptr(cat.t)
+        off = rz[0].arg("y") - _ptr(cat.t)
         src = _buf(e, "drop") if plain else _buf(e, "down_pointwise")
-        ok = len(rz) == (2 if twice else 1) and off == (4 * 8 if swap else 0) and rz[0][6] == cat.ld
+        ok = len(rz) == (2 if twice else 1) and off == (4 * 8 if swap else 0) and rz[0].arg("ldy") == cat.ld
         # the skip projection writes the other slice
-        pw = [a for a in ops(e.ops_fwd, "dl3_pwconv_fwd") if a[8] == cat.ld]
-        ok = ok and len(pw) == 1 and pw[0][7] - _ptr(cat.t) == (0 if swap else 4 * 24)
+        pw = [a for a in ops(e.ops_fwd, "dl3_pwconv_fwd") if a.arg("ldy") == cat.ld]
+        ok = ok and len(pw) == 1 and pw[0].arg("y") - _ptr(cat.t) == (0 if swap else 4 * 24)
         if plain:     # straight into the source's gradient buffer
-            ok = ok and all(a[2] == _ptr(src.grad) and a[3] == src.ld for a in rb)
-            ok = ok and [a[10] for a in rb] == ([0, 1] if twice else [0])
+            ok = ok and all(vals(a, "dx", "lddx") == [_ptr(src.grad), src.ld] for a in rb)
+            ok = ok and [a.arg("accumulate") for a in rb] == ([0, 1] if twice else [0])
         else:         # through tmp and dl3_grad_finish: the source carries BatchNorm and an activation
             b = names(e.ops_bwd)
-            ok = ok and len(rb) == 1 and rb[0][2] != _ptr(src.grad) and b[b.index("dl3_resize_bilinear_bwd") + 1] == "dl3_grad_finish"
+            ok = (ok and len(rb) == 1 and rb[0].arg("dx") != _ptr(src.grad)
+                  and b[b.index("dl3_resize_bilinear_bwd") + 1] == "dl3_grad_finish")
         return ok
     return pred
 
@@ -512,17 +520,18 @@ def p_stems(e):
     f, b = names(e.ops_fwd), names(e.ops_bwd)
     d = ops(e.ops_fwd, "dl3_conv3x3_fwd")
     sink = ops(e.ops_bwd, "dl3_conv3x3_mfma_bwd_data")
-    return (len(d) == 1 and d[0][9:12] == [3, 32, 2] and "dl3_conv3x3_mfma_fwd" in f and "dl3_conv3x3_mfma_bwd_weight" in b
+    return (len(d) == 1 and vals(d[0], "Cin", "Cout", "stride") == [3, 32, 2] and "dl3_conv3x3_mfma_fwd" in f and "dl3_conv3x3_mfma_bwd_weight" in b
             and "dl3_conv3x3_bwd_weight" in b and "dl3_conv3x3_bwd_data" not in b
             # the MFMA bwd-data masks with the input's activation and reduces its BatchNorm's sums
-            and len(sink) == 1 and sink[0][10] == 1 and sink[0][8] is not None and sink[0][12] is not None)
+            and len(sink) == 1 and sink[0].arg("in_act") == 1 and sink[0].arg("in_scale") is not None
+            and sink[0].arg("x_mean") is not None)
 
 
 def p_frozen_res(e):
     p = names(e.ops_prep)
     return (not e.bn_batch and p.count("dl3_bn_frozen_centered") == 3 and p.count("dl3_bn_frozen") == 1
             and "dl3_bn_finalize_direct" not in names(e.ops_fwd) and len(_buf(e, "stem").centred) == 1
-            and all(a[8] == 0 for a in ops(e.ops_bwd, "dl3_bn_bwd_finalize")) and p_residual(e))
+            and all(a.arg("batch_mode") == 0 for a in ops(e.ops_bwd, "dl3_bn_bwd_finalize")) and p_residual(e))
 
 
 def p_frozen_aspp(e):
@@ -530,17 +539,18 @@ def p_frozen_aspp(e):
     add = ops(e.ops_fwd, "dl3_pwconv_fwd_add")
     proj = _buf(e, "concat_projection")
     # the per-image unit of the split projection subtracts the moving mean; the per-pixel GEMM keeps a free bias slot
-    return (not e.bn_batch and len(rows) == 2 and rows[1][6] == proj.vptr(7) and add[0][6] is None and 0 in proj.centred
+    return (not e.bn_batch and len(rows) == 2 and rows[1].arg("bias") == proj.vptr(7) and add[0].arg("bias") is None
+            and 0 in proj.centred
             and sorted(_cat(e).centred) == [0, 16, 32])
 
 
 def p_pruned(e):
     b = names(e.ops_bwd)
     frozen = [u for u in e.units if not u.outv.buf.requires_grad]
-    mid = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_weight") if a[13] is not None and a[15:17] == [16, 16]]
+    mid = [a for a in ops(e.ops_bwd, "dl3_pwconv_bwd_weight") if a.arg("dbias") is not None and vals(a, "K", "N") == [16, 16]]
     return (len(frozen) == 5 and not any(e.trainable(n) for n in e.slots if n.startswith(("stem", "b1_")))
             and b.count("dl3_dwconv3x3_bwd") == 1 and len(mid) == 1
-            and not any(a[23:25] == [16, 16] and a[14] == 0 for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data")))
+            and not any(vals(a, "K", "N", "in_act") == [16, 16, 0] for a in ops(e.ops_bwd, "dl3_pwconv_bwd_data")))
 
 
 def p_pad_residual(e):
@@ -563,7 +573,7 @@ def p_epilogue_stats(e):
 
 def p_relu_of_relu(e):
     d = ops(e.ops_fwd, "dl3_dwconv3x3_fwd")
-    return len(d) == 1 and d[0][3] == 1 and d[0][1] is not None
+    return len(d) == 1 and d[0].arg("in_act") == 1 and d[0].arg("in_scale") is not None
 
 
 def p_two_bn_add(e):
@@ -572,8 +582,8 @@ def p_two_bn_add(e):
     g = u.outv.buf.grad
     gf = ops(e.ops_bwd, "dl3_grad_finish")
     # both inputs alias g; each pass reads and writes g in place (no mask: the identity) and reduces its own buffer's sums
-    return (len(gf) == 2 and u.a.buf.grad is g and u.b.buf.grad is g and all(a[0] == a[4] == _ptr(g) for a in gf)
-            and {a[8] for a in gf} == {_ptr(u.a.buf.t), _ptr(u.b.buf.t)})
+    return (len(gf) == 2 and u.a.buf.grad is g and u.b.buf.grad is g and all(a.arg("gin") == a.arg("gout") == _ptr(g) for a in gf)
+            and {a.arg("xraw") for a in gf} =={_ptr(u.a.buf.t), _ptr(u.b.buf.t)})
 
 
 def both(*preds):

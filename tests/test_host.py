@@ -533,6 +533,10 @@ def _dry_engine(monkeypatch, backbone, B, size=512, OS=16, **kw):
     return e, collections.Counter(op[0] for op in e.ops_fwd + e.ops_bwd)
 
 
+def _mkn(op):
+    return [op.arg(k) for k in "MKN"]
+
+
 def test_knob_table_is_current():
     """KNOBS.md (tools/knobs.py) lists exactly the DL3_* environment variables the sources read — 23 since round 6 removed
     the settled tuning aids — each with default, kind and meaning"""
@@ -576,9 +580,9 @@ def test_default_kernel_routes_by_name(monkeypatch):
     assert L.dl3_pwconv_route(0, 2 * 64 * 64, 160, 960) == R["tiled"]
     # ... and through a lowered plan: the launches of the B=128 engine that take each route
     e, c = _dry_engine(monkeypatch, "mobilenetv2", 128)
-    fwd = [L.dl3_pwconv_route(0, op[2][9], op[2][10], op[2][11]) for op in e.ops_fwd if op[0] == "dl3_pwconv_fwd"]
+    fwd = [L.dl3_pwconv_route(0, *_mkn(op)) for op in e.ops_fwd if op[0] == "dl3_pwconv_fwd"]
     assert fwd.count(R["ws_mfma"]) == 10 and fwd.count(R["ws_hbm"]) == 12 and fwd.count(R["narrow"]) == 1
-    wg = [L.dl3_pwconv_route(2, op[2][14], op[2][15], op[2][16]) for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_weight_dy"]
+    wg = [L.dl3_pwconv_route(2, *_mkn(op)) for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_weight_dy"]
     assert wg.count(R["wgrad_row"]) == 6
     # the statistic partial rows the engine sized cover the weight-stationary kernel's one row per row group
     assert L.dl3_pwconv_partials(M, 160, 960) >= 42 and L.dl3_pwconv_partials(M, 960, 160) >= 42
@@ -621,14 +625,15 @@ def test_act_only_view_reaches_the_narrow_weight_gradient(monkeypatch):
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
     e = Engine(_act_only_logits_model(G), batch=2, training=True, device="cpu")
-    wg = [op[2] for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_weight" and op[2][15:17] == [256, 21]]
+    wg = [op for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_weight" and _mkn(op)[1:] == [256, 21]]
     assert len(wg) == 1
-    a = wg[0]
-    assert a[2] is None and a[3] is None and a[4] == capi.ACT_RELU and a[14] == 131072
-    assert a[12] is not None and a[13] is not None            # dw and the bias gradient: folded by the launch
-    assert L.dl3_pwconv_route(4, a[14], a[15], a[16]) == 5
-    bd = [op[2] for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_data" and op[2][22:25] == [131072, 256, 21]]
-    assert len(bd) == 1 and bd[0][10] is not None and bd[0][12] is None and bd[0][13] is None and bd[0][14] == capi.ACT_RELU
+    w = wg[0]
+    assert w.arg("in_scale") is None and w.arg("in_shift") is None and w.arg("in_act") == capi.ACT_RELU and w.arg("M") == 131072
+    assert w.arg("dw") is not None and w.arg("dbias") is not None   # dw and the bias gradient: folded by the launch
+    assert L.dl3_pwconv_route(4, *_mkn(w)) == 5
+    bd = [op for op in e.ops_bwd if op[0] == "dl3_pwconv_bwd_data" and _mkn(op) == [131072, 256, 21]]
+    assert len(bd) == 1 and bd[0].arg("x") is not None and bd[0].arg("in_scale") is None and bd[0].arg("in_shift") is None
+    assert bd[0].arg("in_act") == capi.ACT_RELU
 
 
 def test_benchmarked_plan_lowers_consistently_without_a_gpu(monkeypatch):
@@ -641,11 +646,11 @@ def test_benchmarked_plan_lowers_consistently_without_a_gpu(monkeypatch):
     L = capi.lib()
     e, c = _dry_engine(monkeypatch, "mobilenetv2", 128)
     assert c["dl3_pwconv_bwd_fused"] == 12 and c["dl3_pwconv_bwd_weight_dy"] == 20
-    ws = [op for op in e.ops_fwd if op[0] == "dl3_pwconv_fwd" and L.dl3_pwconv_fwd_impl(op[2][9], op[2][10], op[2][11]) == 1]
-    assert len(ws) == 12 and {(op[2][10], op[2][11]) for op in ws} == {(32, 16), (16, 96), (96, 24), (24, 144), (144, 24),
-                                                                      (144, 32), (32, 192), (192, 32)}
+    ws = [op for op in e.ops_fwd if op[0] == "dl3_pwconv_fwd" and L.dl3_pwconv_fwd_impl(*_mkn(op)) == 1]
+    assert len(ws) == 12 and {(op.arg("K"), op.arg("N")) for op in ws} == {(32, 16), (16, 96), (96, 24), (24, 144), (144, 24),
+                                                                          (144, 32), (32, 192), (192, 32)}
     for op in ws:   # the statistic partial buffer the engine sized covers the kernel's one row per workgroup
-        assert L.dl3_pwconv_partials(op[2][9], op[2][10], op[2][11]) >= 768
+        assert L.dl3_pwconv_partials(*_mkn(op)) >= 768
     assert e.dy_buf is not None and c["dl3_count_nonzero"] == 1
     e2, c2 = _dry_engine(monkeypatch, "mobilenetv2", 2)
     assert c2["dl3_pwconv_bwd_fused"] == 6            # only the 256x256 / 128x128 layers have >= 32768 rows at B=2
@@ -657,13 +662,71 @@ def test_benchmarked_plan_lowers_consistently_without_a_gpu(monkeypatch):
     # data parallel: the shard's count(w != 0) and loss sum are written INTO the gradient arena's tail
     e4, c4 = _dry_engine(monkeypatch, "mobilenetv2", 2, external_nnz=True)
     cnt = [op for op in e4.ops_fwd if op[0] == "dl3_count_nonzero"][0]
-    assert cnt[2][2] == e4.grads.data_ptr() + 4 * e4.tail and e4.grads.numel() == e4.tail + 4
+    assert cnt.arg("out") == e4.grads.data_ptr() + 4 * e4.tail and e4.grads.numel() == e4.tail + 4
     red = [op for op in e4.ops_fwd if op[0] == "dl3_reduce_partials"][-1]
-    assert red[2][3] == e4.grads.data_ptr() + 4 * (e4.tail + 1) == e4.loss.data_ptr()
+    assert red.arg("out") == e4.grads.data_ptr() + 4 * (e4.tail + 1) == e4.loss.data_ptr()
     assert e4.nnz_host == 512 * 512 and float(e4.nnz[0]) == 512 * 512
     # Xception OS=8: no fused launches (no layer small enough), dY materialised for its 1x1 convolutions
     e5, c5 = _dry_engine(monkeypatch, "xception", 1, size=256, OS=8)
     assert c5["dl3_pwconv_bwd_fused"] == 0 and c5["dl3_pwconv_bwd_weight_dy"] > 50
+
+
+def test_launch_records_read_and_patch_by_the_headers_names(monkeypatch):
+    """engine.Launch: a record still unpacks as (name, fn, args, ws_index) with args in the header's order, and its named
+    reads and writes address those same slots; Engine.op refuses a wrong argument count while lowering; a ws= launch gets
+    the scratch pointer at the slot the header calls `workspace`"""
+    e, c = _dry_engine(monkeypatch, "mobilenetv2", 2, size=64)
+    for entry in ("dl3_pwconv_fwd", "dl3_pwconv_bwd_data", "dl3_pwconv_bwd_weight_dy", "dl3_dwconv3x3_bwd"):
+        rec = [r for r in e.ops_fwd + e.ops_bwd if r[0] == entry][0]
+        name, fn, args, ws_index = rec
+        header = [a for _, a in capi.protos()[entry][1]]
+        assert name == entry and header[-1] == "stream" and len(args) == len(header) - 1 and type(args) is list
+        assert [rec.arg(k) for k in header[:-1]] == args and rec[2] is args
+        for i in (0, len(args) - 1):
+            old = args[i]
+            rec.set(header[i], "patched")
+            assert args[i] == "patched" and rec.arg(header[i]) == "patched"
+            rec.set(header[i], old)
+        for bad in (rec.arg, lambda k: rec.set(k, 0)):
+            with pytest.raises(ValueError, match=r"%s has no parameter 'stream'.*\b%s\b" % (entry, header[-2])):
+                bad("stream")
+    n = len(e.ops_bwd)
+    with pytest.raises(TypeError, match=r"dl3_reduce_partials takes 4 arguments .* 3 were recorded"):
+        e.op(e.ops_bwd, "dl3_reduce_partials", 0, 1, 1)
+    assert len(e.ops_bwd) == n
+    # the launches that share the scratch: patched at `workspace`, which is where ws_index points
+    shared = [r for r in e.ops_bwd if r[3] is not None]
+    assert shared and {r[0] for r in shared} == {"dl3_pwconv_bwd_weight"}
+    for r in shared:
+        header = [a for _, a in capi.protos()[r[0]][1]]
+        assert header[r[3]] == "workspace" and r[2][r[3]] == r.arg("workspace") == e.scratch.data_ptr()
+        assert 0 < r.arg("workspace_bytes") <= e.scratch_bytes
+    rec = e.op([], "dl3_resize_bilinear_bwd", 0, 4, 0, 4, 1, 2, 2, 4, 4, 4, 0, 0, 64, ws=64)
+    assert rec[3] == 11 and rec in e._scratch_users and id(rec) not in e._side
+
+
+def test_bench_reads_the_positions_the_header_names():
+    """bench.py::_work decodes launch arguments by position (it is the yardstick and stays as it is): every position it
+    reads holds the parameter it means — a parameter added in front of one of them has to move bench.py along"""
+    def geom(first):   # N H W C stride rate pad_t pad_l Ho Wo, of which bench.py reads all but the padding
+        return {first + i: k for i, k in enumerate(("N", "H", "W", "C", "stride", "rate", None, None, "Ho", "Wo")) if k}
+    dw_bwd = {1: "yraw", 10: "dx", 11: "dx_add"}
+    table = {
+        "dl3_pwconv_fwd": {9: "M", 10: "K", 11: "N"},
+        "dl3_pwconv_fwd_add": {9: "M", 10: "K", 11: "N"},
+        "dl3_pwconv_bwd_data": {2: "yraw", 10: "x", 15: "dx_add", 22: "M", 23: "K", 24: "N"},
+        "dl3_pwconv_bwd_weight": {7: "yraw", 14: "M", 15: "K", 16: "N"},
+        "dl3_pwconv_bwd_weight_dy": {7: "yraw", 14: "M", 15: "K", 16: "N"},
+        "dl3_pwconv_bwd_fused": {0: "x", 7: "yraw", 16: "dx_add", 18: "stat_x", 23: "M", 24: "K", 25: "N"},
+        "dl3_dwconv3x3_fwd": geom(6),
+        "dl3_dwconv3x3_bwd": {**dw_bwd, **geom(16)},
+        "dl3_dwconv3x3_bwd_sx": {**dw_bwd, 12: "stat_x", **geom(17)},
+        "dl3_reduce_partials_batched": {1: "m"},
+    }
+    protos = capi.parse_header()
+    for entry, at in table.items():
+        header = [a for _, a in protos[entry][1]]
+        assert {i: header[i] for i in at} == at, entry
 
 
 def _plan_table_tool():

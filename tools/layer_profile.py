@@ -32,7 +32,8 @@ torch.cuda.synchronize()
 st = torch.cuda.current_stream().cuda_stream
 rows = []
 for phase, ops in (("fwd", eng.ops_fwd), ("bwd", eng.ops_bwd)):
-    for name, fn, a, _ in ops:
+    for rec in ops:
+        name, fn, a, _ = rec
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(3):
@@ -41,7 +42,7 @@ for phase, ops in (("fwd", eng.ops_fwd), ("bwd", eng.ops_bwd)):
         torch.cuda.synchronize()
         assert rc == 0
         dims = [x for x in a if isinstance(x, int) and 0 < x < 10 ** 7]
-        rows.append((e0.elapsed_time(e1) / 3, phase, name, dims[-8:], a))
+        rows.append((e0.elapsed_time(e1) / 3, phase, name, dims[-8:], rec))
 tot = sum(r[0] for r in rows)
 print("total %.3f ms for %d launches (batch %d)" % (tot, len(rows), args.batch))
 by = {}
@@ -53,14 +54,13 @@ print("top launches:")
 for ms, ph, name, d, _ in sorted(rows, key=lambda r: -r[0])[:args.top]:
     print("  %7.3f ms %-4s %-26s %s" % (ms, ph, name, d))
 if args.gemm:
-    # M, K, N positions in the C signatures (include/dl3.h); bytes = operands read + result written
-    pos = {"dl3_pwconv_fwd": (9, 10, 11), "dl3_pwconv_bwd_data": (22, 23, 24), "dl3_pwconv_bwd_weight": (14, 15, 16)}
+    # bytes = operands read + result written
     agg = {}
-    for ms, ph, name, d, a in rows:
-        if name not in pos:
+    for ms, ph, name, d, rec in rows:
+        if name not in ("dl3_pwconv_fwd", "dl3_pwconv_bwd_data", "dl3_pwconv_bwd_weight"):
             continue
-        M, K, N = (a[i] for i in pos[name])
-        two = a[2] is not None if name == "dl3_pwconv_bwd_data" else (a[7] is not None if name == "dl3_pwconv_bwd_weight" else False)
+        M, K, N = (rec.arg(k) for k in "MKN")
+        two = name != "dl3_pwconv_fwd" and rec.arg("yraw") is not None
         if name == "dl3_pwconv_fwd":
             by_ = 4.0 * (M * K + M * N + K * N)
         elif name == "dl3_pwconv_bwd_data":

@@ -190,8 +190,7 @@ def record(eng):
         rows = []
         for i, op in enumerate(ops):
             name, _, args, ws = op
-            types_ = [t for t, _ in protos[name][1]][:-1]   # (the trailing stream is the replay's)
-            assert len(types_) == len(args), (name, len(types_), len(args))
+            types_ = [t for t, _ in protos[name][1]][:-1]   # (the trailing stream is the replay's; Engine.op checked the count)
             vals = [A.norm(a, "%s[%d] %s arg %d" % (sec, i, name, j)) if t.endswith("*") else _scalar(a)
                     for j, (t, a) in enumerate(zip(types_, args))]
             rows.append([name, vals, ws, id(op) in eng._side, id(op) in eng._join_before])

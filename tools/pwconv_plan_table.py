@@ -62,8 +62,8 @@ def rows_for(shapes, L=None):
              L.dl3_pwconv_bwd_weight_splits(M, K, N, 1)] for M, K, N in shapes]
 
 
-MKN_AT = {"dl3_pwconv_fwd": 9, "dl3_pwconv_fwd_add": 9, "dl3_pwconv_fwd_rows": 9, "dl3_pwconv_bwd_data": 22,
-          "dl3_pwconv_bwd_weight": 14, "dl3_pwconv_bwd_weight_dy": 14}
+PW_LAUNCHES = ("dl3_pwconv_fwd", "dl3_pwconv_fwd_add", "dl3_pwconv_fwd_rows", "dl3_pwconv_bwd_data", "dl3_pwconv_bwd_weight",
+               "dl3_pwconv_bwd_weight_dy")
 
 
 def plan_shapes(backbone, B, size=512, OS=16, head="deeplab"):
@@ -85,7 +85,7 @@ def plan_shapes(backbone, B, size=512, OS=16, head="deeplab"):
     else:
         m = SegModel(image_size=(size, size)).create_seg_model(head, n=21, backbone=backbone)
     e = Engine(m, batch=B, training=True, device="cpu")
-    return sorted({tuple(op[2][MKN_AT[op[0]]:MKN_AT[op[0]] + 3]) for op in e.ops_fwd + e.ops_bwd if op[0] in MKN_AT})
+    return sorted({tuple(op.arg(k) for k in "MKN") for op in e.ops_fwd + e.ops_bwd if op[0] in PW_LAUNCHES})
 
 
 def test_shapes():

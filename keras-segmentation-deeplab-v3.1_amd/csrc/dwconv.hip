@@ -14,6 +14,11 @@
 //
 // BatchNorm + ReLU6 of the producer are applied on load ("input transform"); the BN batch
 // statistics of THIS layer's output are reduced in the epilogue into deterministic partials.
+//
+// What the six kernels share is written once: the per-lane channel operands (DwChan, dw_chan), the gradient operand
+// (dw_dy), the two epilogues (dw_store_stats, dw_store_wgrad) and, for the march kernels, the launch geometry (DwMarch),
+// the tile and row-phase decode (dw_tile, dw_phase) and the driver of the row groups (dw_walk).  A kernel keeps its own
+// row-group body: that is where the three march kernels differ.
 #include "common.h"
 
 // Contraction by the language rule only (a * b + c inside ONE expression becomes a fused multiply-add; nothing is fused
@@ -40,6 +45,42 @@ struct DwGeom {
   int N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo;
   int prows;  // rows of the caller's partial buffers (dl3_dwconv3x3_partials); the launch writes gridDim.y of them
 };
+
+// what a march launch is told (the decomposition of dw_plan), one by-value argument as DwGeom is for the gather kernels
+struct DwMarch {
+  int H, W, C, r, nchunk, TK, nxseg, nphase, ppb, nslab, ny, N;
+  int prows;  // as in DwGeom; the launch writes N * ny * nxseg of them
+  int fast;   // straight-line interior row groups (set in dw_prepare)
+};
+
+// ---- the per-lane channel operands (4 channels from c on) of all six kernels -----------
+struct DwChan {
+  f32x4 wv[9], s, t;         // the nine taps; the input transform act(s * x + t)
+  f32x4 kA, kB, kC, mu, is;  // backward: dY = kA * g + kB * yraw + kC (dw_dy); x_hat = (x - mu) * is of the BatchNorm sums
+};
+// Clamped: C % 4 == 0 and C > 0 (dw_check), so every lane loads in bounds and no load sits in a branch.  A lane with
+// c >= C holds the operands of the last channel quad; it stores nothing (march kernels) or does no work (gather kernels).
+// The forward kernels pass no backward operand and use none of those fields.
+__device__ __forceinline__ DwChan dw_chan(int c, int C, const float *w, const float *sc, const float *sh,
+                                          const float *cA = nullptr, const float *cB = nullptr, const float *cC = nullptr,
+                                          bool stats = false, const float *xmean = nullptr, const float *xinvstd = nullptr) {
+  DwChan cn;
+  const int c4 = min(c, C - 4);
+#pragma unroll
+  for (int i = 0; i < 9; i++) cn.wv[i] = ld4(w + (size_t)i * C + c4);
+  cn.s = splat4(1.f); cn.t = splat4(0.f);
+  cn.kA = splat4(1.f); cn.kB = splat4(0.f); cn.kC = splat4(0.f); cn.mu = splat4(0.f); cn.is = splat4(0.f);
+  if (sc) { cn.s = ld4(sc + c4); cn.t = ld4(sh + c4); }
+  if (cA) { cn.kA = ld4(cA + c4); cn.kB = ld4(cB + c4); cn.kC = ld4(cC + c4); }
+  if (stats) { cn.mu = ld4(xmean + c4); cn.is = ld4(xinvstd + c4); }
+  return cn;
+}
+
+// the gradient with respect to this layer's output from the upstream gradient gv and the layer's raw output yv (BatchNorm
+// backward folded into three per-channel coefficients).  Without coefficients (cA == NULL) dY = g: the second stream then
+// aliases the first (coefficient 0), which dw_yr chooses.
+__device__ __forceinline__ f32x4 dw_dy(const DwChan &cn, f32x4 gv, f32x4 yv) { return cn.kA * gv + cn.kB * yv + cn.kC; }
+__device__ __forceinline__ const float *dw_yr(const float *cA, const float *yraw, const float *g) { return cA ? yraw : g; }
 
 // ---- block reduction over the 32 pixel lanes that share a channel quad -----------------
 // lane layout: tid = pl*8 + cq.  Result valid in threads tid < 8 (pl == 0), fixed order.
@@ -87,20 +128,55 @@ __device__ __forceinline__ void pad_w_partial(float *wpart, int p, int written, 
     for (int i = 0; i < 9; i++) st4(wpart + ((size_t)q * 9 + i) * C + c, splat4(0.f));
 }
 
+// ---- the two epilogues: row p of `written` rows this grid writes, of the buffer's `rows` -----
+// BatchNorm sums (s1: sum, s2: sum of squares or of products) of this workgroup into part[p]; part may be NULL
+__device__ __forceinline__ void dw_store_stats(float *part, int p, int written, int rows, int C, int c, f32x4 s1, f32x4 s2,
+                                               float *red /* [4][8][8] */) {
+  if (!part) return;
+  float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
+  reduce_px<8>(v, red);
+  if (threadIdx.x < 8 && c < C) {
+    f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
+    write_stat_partial(part, p, C, c, r1, r2);
+    pad_stat_partial(part, p, written, rows, C, c);
+  }
+}
+// the nine weight-gradient taps of this workgroup into wpart[p]
+__device__ __forceinline__ void dw_store_wgrad(float *wpart, int p, int written, int rows, int C, int c, const f32x4 (&dwv)[9],
+                                               float *red /* [4][8][36] */) {
+  float v[36];
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    v[i * 4 + 0] = dwv[i].x; v[i * 4 + 1] = dwv[i].y; v[i * 4 + 2] = dwv[i].z; v[i * 4 + 3] = dwv[i].w;
+  }
+  reduce_px<36>(v, red);
+  if (threadIdx.x < 8 && c < C) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      f32x4 o = {v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
+      st4(wpart + ((size_t)p * 9 + i) * C + c, o);
+    }
+    // the partial buffers hold max(forward plan, backward plan) rows and the folds read all of them: the two-pixel
+    // forward halves nxseg and may then halve TK once more, so its plan can be the LARGER one (8 x 64 x 64 x 960 at
+    // rate 16: 128 forward rows, 96 backward) — the rows this grid does not own are zeroed here as in the forward
+    pad_w_partial(wpart, p, written, rows, C, c);
+  }
+}
+
 // Workgroup -> tile decode for the march kernels.  The grid is 1-D and padded to a multiple of 8: hardware hands
 // consecutive workgroup ids to the 8 XCDs round-robin, so id L runs on XCD L%8.  Virtual id v = (L%8)*chunk + L/8
 // makes consecutive v share an XCD (and its 4 MB L2) at about the same time; with the x segment as the fastest
 // coordinate the +-rate taps that cross a 32-pixel segment boundary are served by that L2 instead of a second HBM
-// fetch (at rate 36 on a 64 wide map every tap crosses).
+// fetch (at rate 36 on a 64 wide map every tap crosses).  (The plain order v = L was the round-1 A/B.)
 struct DwTile { int xs, slab, pc, n; };
-__device__ __forceinline__ bool dw_tile(int nxseg, int nslab, int ny, int N, int xcd, DwTile &t) {
+__device__ __forceinline__ bool dw_tile(const DwMarch &M, DwTile &t) {
   const int L = blockIdx.x, chunk = gridDim.x >> 3;
-  int v = xcd ? (L & 7) * chunk + (L >> 3) : L;
-  if (v >= nxseg * nslab * ny * N) return false;
-  t.xs = v % nxseg; v /= nxseg;
-  t.slab = v % nslab; v /= nslab;
-  t.pc = v % ny;
-  t.n = v / ny;
+  int v = (L & 7) * chunk + (L >> 3);
+  if (v >= M.nxseg * M.nslab * M.ny * M.N) return false;
+  t.xs = v % M.nxseg; v /= M.nxseg;
+  t.slab = v % M.nslab; v /= M.nslab;
+  t.pc = v % M.ny;
+  t.n = v / M.ny;
   // (integer division runs on the vector ALU: pin the wave-uniform results to scalar registers, so that the row pointers
   // built from them are scalar and the requests can use the scalar-base + 32-bit-offset address form)
   t.xs = __builtin_amdgcn_readfirstlane(t.xs);
@@ -109,150 +185,160 @@ __device__ __forceinline__ bool dw_tile(int nxseg, int nslab, int ny, int N, int
   t.n = __builtin_amdgcn_readfirstlane(t.n);
   return true;
 }
+// row p of the partial buffers that tile t owns, of N * ny * nxseg
+__device__ __forceinline__ int dw_tile_row(const DwMarch &M, const DwTile &t) { return (t.n * M.ny + t.pc) * M.nxseg + t.xs; }
+
+// Iteration pi of a march workgroup: a workgroup owns `ppb` consecutive row phases (large rates leave only 2-3 rows per
+// phase: several phases per workgroup amortise the prologue) or, for ppb == 1, one chunk of TK rows of one phase.
+// Row slot k of phase a is image row a + k * r; the phase has Ka of them, the chunk is k0 <= k < k1.  False where the
+// workgroup has no phase left.
+struct DwPhase {
+  int a, Ka, k0, k1, Kc;  // Kc: the last slot of the phase, what a row slot is clamped to
+  bool bot_halo;
+  int ks, ke;             // the slots the row walk reads
+};
+__device__ __forceinline__ bool dw_phase(const DwMarch &M, int pc, int pi, DwPhase &ph) {
+  const int a = __builtin_amdgcn_readfirstlane((M.ppb > 1) ? pc * M.ppb + pi : pc / M.nchunk);
+  const int ch = __builtin_amdgcn_readfirstlane((M.ppb > 1) ? 0 : pc % M.nchunk);
+  const int Ka = __builtin_amdgcn_readfirstlane((a < M.H) ? (M.H - a + M.r - 1) / M.r : 0);
+  const int k0 = ch * M.TK;
+  const int k1 = min(k0 + M.TK, Ka);
+  const int Kc = max(Ka - 1, 0);
+  // row slots ks..ke: one halo row above / below the chunk only where the phase continues there (a slot outside the
+  // phase is an all-zero row: skipped, the last row of the phase is flushed after the walk instead)
+  const bool bot_halo = k1 < Ka;
+  const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;
+  ph = DwPhase{a, Ka, k0, k1, Kc, bot_halo, ks, ke};
+  // (one exit, behind the decode, which is plain integer arithmetic for any a: with a `return false` in front of Ka the four
+  // dw_march_bwd instantiations came out 4 to 8 VGPRs larger and <true, true> spilt 28 bytes instead of 12)
+  return a < M.nphase;
+}
+
+// The row walk of a march kernel: slots ks..ke in groups of R rows; group(kg, std::false_type{}) is the kernel's predicated
+// body of rows kg .. kg + R - 1, group(kg, std::true_type{}) its straight-line body.
+// Round 5: INTERIOR groups of a workgroup whose lanes are all inside the tensor (fast_ok) take the straight-line body: every
+// row of the group is a live row whose output row belongs to the chunk (rows up to fast_last), so its R stores are
+// unconditional.  vmcnt retires in order and counts stores; around a store inside a branch the compiler cannot count,
+// assumes it away and sizes the waits for the group's LAST loads as vmcnt(0) — which the hardware reads as "and every store
+// issued so far": each group ended with the wave waiting for its own first stores to be acknowledged.  With the stores
+// counted that wait is vmcnt(3) in dw_march_fwd.  The first group (its first row only feeds the accumulators), the last
+// one(s) and edge workgroups keep the predicated body.  Multiplying by a validity of 1.0 is exact: same values, same sums.
+template <int R, class Group>
+__device__ __forceinline__ void dw_walk(const DwPhase &ph, bool fast_ok, int fast_last, Group &group) {
+  int kg = ph.ks;
+  group(kg, std::false_type{});
+  kg += R;
+  if (fast_ok) {
+    // (enter the straight-line loop with nothing outstanding: a request of the predicated group still pending at the loop
+    // head is merged into every iteration's state and comes back as a vmcnt(0) in front of each group's requests)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    for (; kg + R - 1 <= fast_last; kg += R) group(kg, std::true_type{});
+  }
+  for (; kg <= ph.ke; kg += R) group(kg, std::false_type{});
+}
 
 // ======================================================================================
 // march forward: 1-D grid over (x segment, channel slab, row phase/chunk, image), block 256
 // ======================================================================================
 __global__ __launch_bounds__(256, 3) void dw_march_fwd(const float *__restrict__ x, const float *__restrict__ sc,
                                                     const float *__restrict__ sh, int act,
-                                                    const float *__restrict__ w, float *__restrict__ y,
-                                                    int H, int W, int C, int r, int nchunk, int TK, int nxseg,
-                                                    int nphase, int ppb, int nslab, int ny, int N, int xcd,
-                                                    float *__restrict__ part, int prows, int fast) {
+                                                    const float *__restrict__ w, float *__restrict__ y, DwMarch M,
+                                                    float *__restrict__ part) {
   __shared__ float red[4 * 8 * 8];
   const int tid = threadIdx.x, cq = tid & 7, pl = tid >> 3;
   DwTile tile;
-  if (!dw_tile(nxseg, nslab, ny, N, xcd, tile)) return;
-  const int xs = tile.xs, slab = tile.slab, pc = tile.pc, n = tile.n;
+  if (!dw_tile(M, tile)) return;
+  const int H = M.H, W = M.W, C = M.C, r = M.r;
+  const int xs = tile.xs, slab = tile.slab, n = tile.n;
   const int c = slab * 32 + cq * 4;
   const int xx = xs * 32 + pl;
   const bool active = (c < C) && (xx < W);
 
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-#pragma unroll
-  for (int i = 0; i < 9; i++) wv[i] = ld4(w + (size_t)i * C + min(c, C - 4));
-  if (sc) { s = ld4(sc + min(c, C - 4)); t = ld4(sh + min(c, C - 4)); }
+  const DwChan cn = dw_chan(c, C, w, sc, sh);
   f32x4 s1 = splat4(0.f), s2 = splat4(0.f);
-  // a workgroup owns `ppb` consecutive row phases (large rates leave only 2-3 rows per phase: several phases per
-  // workgroup amortise the prologue) or, for ppb == 1, one chunk of TK rows of one phase
-  for (int pi = 0; pi < ppb; ++pi) {
-  const int a = __builtin_amdgcn_readfirstlane((ppb > 1) ? pc * ppb + pi : pc / nchunk);
-  const int ch = __builtin_amdgcn_readfirstlane((ppb > 1) ? 0 : pc % nchunk);
-  if (a >= nphase) break;
-  const int Ka = __builtin_amdgcn_readfirstlane((a < H) ? (H - a + r - 1) / r : 0);
-  const int k0 = ch * TK;
-  const int k1 = min(k0 + TK, Ka);
-  const int Kc = max(Ka - 1, 0);
-  const bool xl_ok = (xx - r >= 0), xr_ok = (xx + r < W);
-  // clamped coordinates: every lane always issues in-bounds loads (no branches -> the loads of a row group are
-  // all in flight together); out-of-image taps and idle lanes are zeroed by a select afterwards
-  const int cc = min(c, C - 4), xc = min(xx, W - 1), xlc = min(max(xx - r, 0), W - 1), xrc = min(xx + r, W - 1);
-  // addresses: a wave-uniform row pointer + one 32-bit byte offset per tap (shared by both bodies of the row loop below)
-  const float *xn = x + (size_t)n * H * W * C;
-  float *yn = y + (size_t)n * H * W * C;
-  const unsigned om = 4u * (unsigned)(xc * C + cc), ol = 4u * (unsigned)(xlc * C + cc), orr = 4u * (unsigned)(xrc * C + cc);
-  const unsigned oo = 4u * (unsigned)(xx * C + c);   // own position (stores; == om in an all-active workgroup)
+  for (int pi = 0; pi < M.ppb; ++pi) {
+    DwPhase ph;
+    if (!dw_phase(M, tile.pc, pi, ph)) break;
+    const int a = ph.a;
+    const bool xl_ok = (xx - r >= 0), xr_ok = (xx + r < W);
+    // clamped coordinates: every lane always issues in-bounds loads (no branches -> the loads of a row group are
+    // all in flight together); out-of-image taps and idle lanes are zeroed by a select afterwards
+    const int cc = min(c, C - 4), xc = min(xx, W - 1), xlc = min(max(xx - r, 0), W - 1), xrc = min(xx + r, W - 1);
+    // addresses: a wave-uniform row pointer + one 32-bit byte offset per tap (shared by both bodies of the row loop below)
+    const float *xn = x + (size_t)n * H * W * C;
+    float *yn = y + (size_t)n * H * W * C;
+    const unsigned om = 4u * (unsigned)(xc * C + cc), ol = 4u * (unsigned)(xlc * C + cc), orr = 4u * (unsigned)(xrc * C + cc);
+    const unsigned oo = 4u * (unsigned)(xx * C + c);   // own position (stores; == om in an all-active workgroup)
 
-  auto ldrow = [&](int k, f32x4 &l, f32x4 &m, f32x4 &rr) {
-    const bool rok = active && k >= 0 && k < Ka;
-    const float *row = xn + (size_t)(a + min(max(k, 0), Kc) * r) * W * C;
-    const f32x4 vm = dl3_act4(s * ld4_su(row, om) + t, act);
-    const f32x4 vl = dl3_act4(s * ld4_su(row, ol) + t, act);
-    const f32x4 vr = dl3_act4(s * ld4_su(row, orr) + t, act);
-    // multiply by 0/1 instead of selecting: a select lets the compiler sink the loads into a branch again
-    m = vm * splat4(rok ? 1.f : 0.f);
-    l = vl * splat4((rok && xl_ok) ? 1.f : 0.f);
-    rr = vr * splat4((rok && xr_ok) ? 1.f : 0.f);
-  };
+    auto ldrow = [&](int k, f32x4 &l, f32x4 &m, f32x4 &rr) {
+      const bool rok = active && k >= 0 && k < ph.Ka;
+      const float *row = xn + (size_t)(a + min(max(k, 0), ph.Kc) * r) * W * C;
+      const f32x4 vm = dl3_act4(cn.s * ld4_su(row, om) + cn.t, act);
+      const f32x4 vl = dl3_act4(cn.s * ld4_su(row, ol) + cn.t, act);
+      const f32x4 vr = dl3_act4(cn.s * ld4_su(row, orr) + cn.t, act);
+      // multiply by 0/1 instead of selecting: a select lets the compiler sink the loads into a branch again
+      m = vm * splat4(rok ? 1.f : 0.f);
+      l = vl * splat4((rok && xl_ok) ? 1.f : 0.f);
+      rr = vr * splat4((rok && xr_ok) ? 1.f : 0.f);
+    };
 
-  f32x4 accA = splat4(0.f), accB = splat4(0.f);
-  // rows are processed in groups of R: all 3*R loads of a group are issued before the first use, so every lane
-  // keeps R cache-missing (centre-tap) loads in flight — the kernel is latency-bound otherwise
-  constexpr int R = 4;
-  // input row slots ks..ke: one halo row above / below the chunk only where the phase continues there (a slot
-  // outside the phase is an all-zero row: skipped, the last output row is flushed after the loop instead)
-  const bool bot_halo = k1 < Ka;
-  const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;
-  // Round 5: INTERIOR groups of a workgroup whose lanes are all inside the tensor take a straight-line body: every row
-  // of the group is a live row whose output row belongs to the chunk, so its R stores are unconditional.  vmcnt retires
-  // in order and counts stores; around a store inside a branch the compiler cannot count, assumes it away and sizes the
-  // waits for the group's LAST loads as vmcnt(0) — which the hardware reads as "and every store issued so far": each group
-  // ended with the wave waiting for its own first three stores to be acknowledged.  With the stores counted that wait is
-  // vmcnt(3).  The first group (its first row only feeds the accumulators), the last one(s) and edge workgroups keep the
-  // predicated body.  Multiplying by a validity of 1.0 is exact: same values, same sums.
-  const bool allact = fast && (slab * 32 + 32 <= C) && (xs * 32 + 32 <= W);
-  auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {
-    constexpr bool FAST = decltype(fastc)::value;
-    f32x4 l[R], m[R], rr[R];
+    f32x4 accA = splat4(0.f), accB = splat4(0.f);
+    // rows are processed in groups of R: all 3*R loads of a group are issued before the first use, so every lane
+    // keeps R cache-missing (centre-tap) loads in flight — the kernel is latency-bound otherwise
+    constexpr int R = 4;
+    const bool allact = M.fast && (slab * 32 + 32 <= C) && (xs * 32 + 32 <= W);
+    auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {
+      constexpr bool FAST = decltype(fastc)::value;
+      f32x4 l[R], m[R], rr[R];
 #pragma unroll
-    for (int j = 0; j < R; j++) {
-      if constexpr (FAST) {
-        // (wave-uniform row pointer + a 32-bit lane offset: one address register per tap instead of a 64-bit pair per request)
-        const float *row = xn + (size_t)(a + (kg + j) * r) * W * C;
-        m[j] = dl3_act4(s * ld4_su(row, om) + t, act);
-        l[j] = dl3_act4(s * ld4_su(row, ol) + t, act) * splat4(xl_ok ? 1.f : 0.f);
-        rr[j] = dl3_act4(s * ld4_su(row, orr) + t, act) * splat4(xr_ok ? 1.f : 0.f);
-      } else {
-        ldrow((kg + j <= ke) ? kg + j : -1, l[j], m[j], rr[j]);
+      for (int j = 0; j < R; j++) {
+        if constexpr (FAST) {
+          // (wave-uniform row pointer + a 32-bit lane offset: one address register per tap instead of a 64-bit pair per request)
+          const float *row = xn + (size_t)(a + (kg + j) * r) * W * C;
+          m[j] = dl3_act4(cn.s * ld4_su(row, om) + cn.t, act);
+          l[j] = dl3_act4(cn.s * ld4_su(row, ol) + cn.t, act) * splat4(xl_ok ? 1.f : 0.f);
+          rr[j] = dl3_act4(cn.s * ld4_su(row, orr) + cn.t, act) * splat4(xr_ok ? 1.f : 0.f);
+        } else {
+          ldrow((kg + j <= ph.ke) ? kg + j : -1, l[j], m[j], rr[j]);
+        }
       }
-    }
 #pragma unroll
-    for (int j = 0; j < R; j++) {
-      const int k = kg + j;
-      // (no `if (k > ke) break;` here: a path that leaves the group early leaves the group's remaining requests
-      // un-waited-for, the compiler then has to wait for EVERYTHING at the head of the row loop before it may reuse their
-      // registers.  Rows beyond ke are all-zero slots: predicated instead.  Round 5.)
-      const bool kv = FAST || k <= ke;
-      // input row k feeds out[k+1] (tap row 0), out[k] (tap row 1), out[k-1] (tap row 2)
-      f32x4 h0 = wv[0] * l[j] + wv[1] * m[j] + wv[2] * rr[j];
-      f32x4 h1 = wv[3] * l[j] + wv[4] * m[j] + wv[5] * rr[j];
-      f32x4 h2 = wv[6] * l[j] + wv[7] * m[j] + wv[8] * rr[j];
-      f32x4 out = accA + h2;
-      if constexpr (FAST) {
-        st4_nt_su(yn + (size_t)(a + (k - 1) * r) * W * C, oo, out);
-        s1 += out;
-        s2 += out * out;
-        accA = accB + h1;
-        accB = h0;
-      } else {
-        if (active && kv && k - 1 >= k0 && k - 1 < k1) {
+      for (int j = 0; j < R; j++) {
+        const int k = kg + j;
+        // (no `if (k > ke) break;` here: a path that leaves the group early leaves the group's remaining requests
+        // un-waited-for, the compiler then has to wait for EVERYTHING at the head of the row loop before it may reuse their
+        // registers.  Rows beyond ke are all-zero slots: predicated instead.  Round 5.)
+        const bool kv = FAST || k <= ph.ke;
+        // input row k feeds out[k+1] (tap row 0), out[k] (tap row 1), out[k-1] (tap row 2)
+        f32x4 h0 = cn.wv[0] * l[j] + cn.wv[1] * m[j] + cn.wv[2] * rr[j];
+        f32x4 h1 = cn.wv[3] * l[j] + cn.wv[4] * m[j] + cn.wv[5] * rr[j];
+        f32x4 h2 = cn.wv[6] * l[j] + cn.wv[7] * m[j] + cn.wv[8] * rr[j];
+        f32x4 out = accA + h2;
+        if constexpr (FAST) {
           st4_nt_su(yn + (size_t)(a + (k - 1) * r) * W * C, oo, out);
           s1 += out;
           s2 += out * out;
+          accA = accB + h1;
+          accB = h0;
+        } else {
+          if (active && kv && k - 1 >= ph.k0 && k - 1 < ph.k1) {
+            st4_nt_su(yn + (size_t)(a + (k - 1) * r) * W * C, oo, out);
+            s1 += out;
+            s2 += out * out;
+          }
+          accA = kv ? accB + h1 : accA;
+          accB = kv ? h0 : accB;
         }
-        accA = kv ? accB + h1 : accA;
-        accB = kv ? h0 : accB;
       }
+    };
+    if (ph.k0 < ph.k1) dw_walk<R>(ph, allact, ph.ke, group);
+    if (!ph.bot_halo && ph.k0 < ph.k1 && active) {  // last row of the phase: no row below contributes
+      st4_nt_su(yn + (size_t)(a + (ph.k1 - 1) * r) * W * C, oo, accA);
+      s1 += accA;
+      s2 += accA * accA;
     }
-  };
-  if (k0 < k1) {
-    int kg = ks;
-    group(kg, std::false_type{});
-    kg += R;
-    if (allact) {
-      // (enter the straight-line loop with nothing outstanding: a request of the predicated group still pending at the loop
-      // head is merged into every iteration's state and comes back as a vmcnt(0) in front of each group's requests)
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-      for (; kg + R - 1 <= ke; kg += R) group(kg, std::true_type{});
-    }
-    for (; kg <= ke; kg += R) group(kg, std::false_type{});
-  }
-  if (!bot_halo && k0 < k1 && active) {  // last row of the phase: no row below contributes
-    st4_nt_su(yn + (size_t)(a + (k1 - 1) * r) * W * C, oo, accA);
-    s1 += accA;
-    s2 += accA * accA;
-  }
   }  // phases of this workgroup
-  if (part) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && c < C) {
-      const int p = (n * ny + pc) * nxseg + xs;
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(part, p, C, c, r1, r2);
-      pad_stat_partial(part, p, N * ny * nxseg, prows, C, c);
-    }
-  }
+  dw_store_stats(part, dw_tile_row(M, tile), M.N * M.ny * M.nxseg, M.prows, C, c, s1, s2, red);
 }
 
 // ======================================================================================
@@ -265,24 +351,20 @@ __global__ __launch_bounds__(256, 3) void dw_march_fwd(const float *__restrict__
 // ======================================================================================
 __global__ __launch_bounds__(256, 3) void dw_march2_fwd(const float *__restrict__ x, const float *__restrict__ sc,
                                                      const float *__restrict__ sh, int act,
-                                                     const float *__restrict__ w, float *__restrict__ y,
-                                                     int H, int W, int C, int r, int nchunk, int TK, int nxseg,
-                                                     int nphase, int ppb, int nslab, int ny, int N, int xcd,
-                                                     float *__restrict__ part, int prows, int fast) {
+                                                     const float *__restrict__ w, float *__restrict__ y, DwMarch M,
+                                                     float *__restrict__ part) {
   __shared__ float red[4 * 8 * 8];
   const int tid = threadIdx.x, cq = tid & 7, pl = tid >> 3;
   DwTile tile;
-  if (!dw_tile(nxseg, nslab, ny, N, xcd, tile)) return;
-  const int xs = tile.xs, slab = tile.slab, pc = tile.pc, n = tile.n;
+  if (!dw_tile(M, tile)) return;
+  const int H = M.H, W = M.W, C = M.C, r = M.r;
+  const int xs = tile.xs, slab = tile.slab, n = tile.n;
   const int c = slab * 32 + cq * 4;
   const int xa = xs * 64 + (pl / r) * 2 * r + pl % r, xb = xa + r;
   const bool ca = c < C;
   const bool act_a = ca && xa < W, act_b = ca && xb < W;
 
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-#pragma unroll
-  for (int i = 0; i < 9; i++) wv[i] = ld4(w + (size_t)i * C + min(c, C - 4));
-  if (sc) { s = ld4(sc + min(c, C - 4)); t = ld4(sh + min(c, C - 4)); }
+  const DwChan cn = dw_chan(c, C, w, sc, sh);
   f32x4 s1 = splat4(0.f), s2 = splat4(0.f);
   const int cc = min(c, C - 4);
   // clamped columns (loads are always in bounds) and 0/1 validity of the four column positions
@@ -295,28 +377,21 @@ __global__ __launch_bounds__(256, 3) void dw_march2_fwd(const float *__restrict_
   const unsigned o0 = 4u * (unsigned)(x0c * C + cc), o1 = 4u * (unsigned)(x1c * C + cc), o2 = 4u * (unsigned)(x2c * C + cc),
                  o3 = 4u * (unsigned)(x3c * C + cc);
   const unsigned osa = 4u * (unsigned)(xa * C + c), osb = 4u * (unsigned)(xb * C + c);  // own positions (stores)
-  for (int pi = 0; pi < ppb; ++pi) {
-    const int a = __builtin_amdgcn_readfirstlane((ppb > 1) ? pc * ppb + pi : pc / nchunk);
-    const int ch = __builtin_amdgcn_readfirstlane((ppb > 1) ? 0 : pc % nchunk);
-    if (a >= nphase) break;
-    const int Ka = __builtin_amdgcn_readfirstlane((a < H) ? (H - a + r - 1) / r : 0);
-    const int k0 = ch * TK;
-    const int k1 = min(k0 + TK, Ka);
-    const int Kc = max(Ka - 1, 0);
+  for (int pi = 0; pi < M.ppb; ++pi) {
+    DwPhase ph;
+    if (!dw_phase(M, tile.pc, pi, ph)) break;
+    const int a = ph.a;
     auto ldrow = [&](int k, f32x4 (&p)[4]) {
-      const float rok = (k >= 0 && k < Ka) ? 1.f : 0.f;
-      const float *row = xn + (size_t)(a + min(max(k, 0), Kc) * r) * W * C;
-      p[0] = dl3_act4(s * ld4_su(row, o0) + t, act) * splat4(rok * v0);
-      p[1] = dl3_act4(s * ld4_su(row, o1) + t, act) * splat4(rok * v1);
-      p[2] = dl3_act4(s * ld4_su(row, o2) + t, act) * splat4(rok * v2);
-      p[3] = dl3_act4(s * ld4_su(row, o3) + t, act) * splat4(rok * v3);
+      const float rok = (k >= 0 && k < ph.Ka) ? 1.f : 0.f;
+      const float *row = xn + (size_t)(a + min(max(k, 0), ph.Kc) * r) * W * C;
+      p[0] = dl3_act4(cn.s * ld4_su(row, o0) + cn.t, act) * splat4(rok * v0);
+      p[1] = dl3_act4(cn.s * ld4_su(row, o1) + cn.t, act) * splat4(rok * v1);
+      p[2] = dl3_act4(cn.s * ld4_su(row, o2) + cn.t, act) * splat4(rok * v2);
+      p[3] = dl3_act4(cn.s * ld4_su(row, o3) + cn.t, act) * splat4(rok * v3);
     };
     f32x4 aA = splat4(0.f), aB = splat4(0.f), bA = splat4(0.f), bB = splat4(0.f);
     constexpr int R = 3;
-    const bool bot_halo = k1 < Ka;
-    const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;
-    // (interior groups of all-active workgroups: straight-line body with counted stores, see dw_march_fwd)
-    const bool allact = fast && (slab * 32 + 32 <= C) && (xs * 64 + 64 <= W);
+    const bool allact = M.fast && (slab * 32 + 32 <= C) && (xs * 64 + 64 <= W);
     auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {
       constexpr bool FAST = decltype(fastc)::value;
       f32x4 p[R][4];
@@ -324,25 +399,25 @@ __global__ __launch_bounds__(256, 3) void dw_march2_fwd(const float *__restrict_
       for (int j = 0; j < R; j++) {
         if constexpr (FAST) {
           const float *row = xn + (size_t)(a + (kg + j) * r) * W * C;   // wave-uniform + 32-bit lane offsets
-          p[j][0] = dl3_act4(s * ld4_su(row, o0) + t, act) * splat4(v0);
-          p[j][1] = dl3_act4(s * ld4_su(row, o1) + t, act) * splat4(v1);
-          p[j][2] = dl3_act4(s * ld4_su(row, o2) + t, act) * splat4(v2);
-          p[j][3] = dl3_act4(s * ld4_su(row, o3) + t, act) * splat4(v3);
+          p[j][0] = dl3_act4(cn.s * ld4_su(row, o0) + cn.t, act) * splat4(v0);
+          p[j][1] = dl3_act4(cn.s * ld4_su(row, o1) + cn.t, act) * splat4(v1);
+          p[j][2] = dl3_act4(cn.s * ld4_su(row, o2) + cn.t, act) * splat4(v2);
+          p[j][3] = dl3_act4(cn.s * ld4_su(row, o3) + cn.t, act) * splat4(v3);
         } else {
-          ldrow((kg + j <= ke) ? kg + j : -1, p[j]);
+          ldrow((kg + j <= ph.ke) ? kg + j : -1, p[j]);
         }
       }
 #pragma unroll
       for (int j = 0; j < R; j++) {
         const int k = kg + j;
-        const bool kv = FAST || k <= ke;   // (predicated, not `break`: see dw_march_fwd)
+        const bool kv = FAST || k <= ph.ke;   // (predicated, not `break`: see dw_march_fwd)
         // pixel a: taps (p0, p1, p2); pixel b: taps (p1, p2, p3)
-        const f32x4 a0 = wv[0] * p[j][0] + wv[1] * p[j][1] + wv[2] * p[j][2];
-        const f32x4 a1 = wv[3] * p[j][0] + wv[4] * p[j][1] + wv[5] * p[j][2];
-        const f32x4 a2 = wv[6] * p[j][0] + wv[7] * p[j][1] + wv[8] * p[j][2];
-        const f32x4 b0 = wv[0] * p[j][1] + wv[1] * p[j][2] + wv[2] * p[j][3];
-        const f32x4 b1 = wv[3] * p[j][1] + wv[4] * p[j][2] + wv[5] * p[j][3];
-        const f32x4 b2 = wv[6] * p[j][1] + wv[7] * p[j][2] + wv[8] * p[j][3];
+        const f32x4 a0 = cn.wv[0] * p[j][0] + cn.wv[1] * p[j][1] + cn.wv[2] * p[j][2];
+        const f32x4 a1 = cn.wv[3] * p[j][0] + cn.wv[4] * p[j][1] + cn.wv[5] * p[j][2];
+        const f32x4 a2 = cn.wv[6] * p[j][0] + cn.wv[7] * p[j][1] + cn.wv[8] * p[j][2];
+        const f32x4 b0 = cn.wv[0] * p[j][1] + cn.wv[1] * p[j][2] + cn.wv[2] * p[j][3];
+        const f32x4 b1 = cn.wv[3] * p[j][1] + cn.wv[4] * p[j][2] + cn.wv[5] * p[j][3];
+        const f32x4 b2 = cn.wv[6] * p[j][1] + cn.wv[7] * p[j][2] + cn.wv[8] * p[j][3];
         const f32x4 oa = aA + a2, ob = bA + b2;
         if constexpr (FAST) {
           float *orow = yn + (size_t)(a + (k - 1) * r) * W * C;
@@ -351,7 +426,7 @@ __global__ __launch_bounds__(256, 3) void dw_march2_fwd(const float *__restrict_
           aA = aB + a1; aB = a0;
           bA = bB + b1; bB = b0;
         } else {
-          if (kv && k - 1 >= k0 && k - 1 < k1) {
+          if (kv && k - 1 >= ph.k0 && k - 1 < ph.k1) {
             float *orow = yn + (size_t)(a + (k - 1) * r) * W * C;
             if (act_a) { st4_nt_su(orow, osa, oa); s1 += oa; s2 += oa * oa; }
             if (act_b) { st4_nt_su(orow, osb, ob); s1 += ob; s2 += ob * ob; }
@@ -361,32 +436,14 @@ __global__ __launch_bounds__(256, 3) void dw_march2_fwd(const float *__restrict_
         }
       }
     };
-    if (k0 < k1) {
-      int kg = ks;
-      group(kg, std::false_type{});
-      kg += R;
-      if (allact) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // (see dw_march_fwd)
-        for (; kg + R - 1 <= ke; kg += R) group(kg, std::true_type{});
-      }
-      for (; kg <= ke; kg += R) group(kg, std::false_type{});
-    }
-    if (!bot_halo && k0 < k1) {  // last row of the phase: no row below contributes
-      float *orow = yn + (size_t)(a + (k1 - 1) * r) * W * C;
+    if (ph.k0 < ph.k1) dw_walk<R>(ph, allact, ph.ke, group);
+    if (!ph.bot_halo && ph.k0 < ph.k1) {  // last row of the phase: no row below contributes
+      float *orow = yn + (size_t)(a + (ph.k1 - 1) * r) * W * C;
       if (act_a) { st4_nt_su(orow, osa, aA); s1 += aA; s2 += aA * aA; }
       if (act_b) { st4_nt_su(orow, osb, bA); s1 += bA; s2 += bA * bA; }
     }
   }
-  if (part) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && c < C) {
-      const int p = (n * ny + pc) * nxseg + xs;
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(part, p, C, c, r1, r2);
-      pad_stat_partial(part, p, N * ny * nxseg, prows, C, c);
-    }
-  }
+  dw_store_stats(part, dw_tile_row(M, tile), M.N * M.ny * M.nxseg, M.prows, C, c, s1, s2, red);
 }
 
 // ======================================================================================
@@ -399,208 +456,159 @@ __global__ __launch_bounds__(256, 2) void dw_march_bwd(
     const float *__restrict__ cB, const float *__restrict__ cC, const float *__restrict__ x,
     const float *__restrict__ sc, const float *__restrict__ sh, int act, const float *__restrict__ w,
     float *__restrict__ dx, const float *__restrict__ dx_add, const float *__restrict__ xmean,
-    const float *__restrict__ xinvstd, float *__restrict__ dpart, float *__restrict__ wpart, int H, int W, int C,
-    int r, int nchunk, int TK, int nxseg, int nphase, int ppb, int nslab, int ny, int N, int xcd, int prows,
-    const float *__restrict__ sx, int fast) {
+    const float *__restrict__ xinvstd, float *__restrict__ dpart, float *__restrict__ wpart, DwMarch M,
+    const float *__restrict__ sx) {
   // sx (nullable, round 4): the BatchNorm-backward sums of dx are taken against x_hat of THIS tensor instead of the
   // forward input — the other input of the residual Add whose output gradient this launch completes (Xception's `sum`
   // shortcuts: the gradient reaches the block's last pointwise BatchNorm unchanged, Engine.alias_stats_target)
   __shared__ float red[4 * 8 * 36];
   const int tid = threadIdx.x, cq = tid & 7, pl = tid >> 3;
   DwTile tile;
-  if (!dw_tile(nxseg, nslab, ny, N, xcd, tile)) return;
-  const int xs = tile.xs, slab = tile.slab, pc = tile.pc, n = tile.n;
+  if (!dw_tile(M, tile)) return;
+  const int H = M.H, W = M.W, C = M.C, r = M.r;
+  const int xs = tile.xs, slab = tile.slab, n = tile.n;
   const int c = slab * 32 + cq * 4;
   const int xx = xs * 32 + pl;
   const bool active = (c < C) && (xx < W);
 
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-  f32x4 kA = splat4(1.f), kB = splat4(0.f), kC = splat4(0.f), mu = splat4(0.f), is = splat4(0.f);
-  {
-    const int c4 = min(c, C - 4);
-#pragma unroll
-    for (int i = 0; i < 9; i++) wv[i] = ld4(w + (size_t)i * C + c4);
-    if (sc) { s = ld4(sc + c4); t = ld4(sh + c4); }
-    if (cA) { kA = ld4(cA + c4); kB = ld4(cB + c4); kC = ld4(cC + c4); }
-    if (dpart) { mu = ld4(xmean + c4); is = ld4(xinvstd + c4); }
-  }
-  const bool two = (cA != nullptr);
+  const DwChan cn = dw_chan(c, C, w, sc, sh, cA, cB, cC, dpart != nullptr, xmean, xinvstd);
   const bool xl_ok = (xx - r >= 0), xr_ok = (xx + r < W);
   const int cc = min(c, C - 4), xc = min(xx, W - 1), xlc = min(max(xx - r, 0), W - 1), xrc = min(xx + r, W - 1);
   // addresses: wave-uniform row pointers + one 32-bit byte offset per tap (shared by both bodies of the row loop)
   const size_t nimg = (size_t)n * H * W * C;
   const unsigned om = 4u * (unsigned)(xc * C + cc), ol = 4u * (unsigned)(xlc * C + cc), orr = 4u * (unsigned)(xrc * C + cc);
   const unsigned oo = 4u * (unsigned)(xx * C + c);   // own position (stores; == om in an all-active workgroup)
-  const bool allact = fast && (slab * 32 + 32 <= C) && (xs * 32 + 32 <= W);
+  const bool allact = M.fast && (slab * 32 + 32 <= C) && (xs * 32 + 32 <= W);
   f32x4 dwv[9];
 #pragma unroll
   for (int i = 0; i < 9; i++) dwv[i] = splat4(0.f);
   f32x4 s1 = splat4(0.f), s2 = splat4(0.f);
-  for (int pi = 0; pi < ppb; ++pi) {  // row phases owned by this workgroup (see dw_march_fwd)
-  const int a = __builtin_amdgcn_readfirstlane((ppb > 1) ? pc * ppb + pi : pc / nchunk);
-  const int ch = __builtin_amdgcn_readfirstlane((ppb > 1) ? 0 : pc % nchunk);
-  if (a >= nphase) break;
-  const int Ka = __builtin_amdgcn_readfirstlane((a < H) ? (H - a + r - 1) / r : 0);
-  const int k0 = ch * TK;
-  const int k1 = min(k0 + TK, Ka);
-  const int Kc = max(Ka - 1, 0);
-  const float *yr = two ? yraw : g;  // when dY = g the second stream aliases the first (coefficient 0)
-  // element offset of row slot k of this phase inside the image (k clamped into the phase: always in bounds)
-  auto rowoff = [&](int k) -> size_t { return nimg + (size_t)(a + min(max(k, 0), Kc) * r) * W * C; };
+  for (int pi = 0; pi < M.ppb; ++pi) {  // row phases owned by this workgroup
+    DwPhase ph;
+    if (!dw_phase(M, tile.pc, pi, ph)) break;
+    const int a = ph.a;
+    const float *yr = dw_yr(cA, yraw, g);
+    // element offset of row slot k of this phase inside the image (k clamped into the phase: always in bounds)
+    auto rowoff = [&](int k) -> size_t { return nimg + (size_t)(a + min(max(k, 0), ph.Kc) * r) * W * C; };
 
-  auto ld_dd1 = [&](size_t row, unsigned off) -> f32x4 { return kA * ld4_su(g + row, off) + kB * ld4_su(yr + row, off) + kC; };
-  auto ld_dd = [&](int k, f32x4 &l, f32x4 &m, f32x4 &rr) {
-    const bool rok = active && k >= 0 && k < Ka;
-    const size_t row = rowoff(k);
-    const f32x4 vm = ld_dd1(row, om), vl = ld_dd1(row, ol), vr = ld_dd1(row, orr);
-    m = vm * splat4(rok ? 1.f : 0.f);
-    l = vl * splat4((rok && xl_ok) ? 1.f : 0.f);
-    rr = vr * splat4((rok && xr_ok) ? 1.f : 0.f);
-  };
-  // forward input row k at own column: raw value and validity
-  auto ld_e = [&](int k, f32x4 &raw, bool &ok) {
-    ok = active && k >= 0 && k < Ka;
-    raw = ld4_su(x + rowoff(k), om);
-  };
-  auto eact = [&](f32x4 raw, bool ok) -> f32x4 {
-    const f32x4 v = dl3_act4(s * raw + t, act);
-    return v * splat4(ok ? 1.f : 0.f);
-  };
+    auto ld_dd1 = [&](size_t row, unsigned off) -> f32x4 { return dw_dy(cn, ld4_su(g + row, off), ld4_su(yr + row, off)); };
+    auto ld_dd = [&](int k, f32x4 &l, f32x4 &m, f32x4 &rr) {
+      const bool rok = active && k >= 0 && k < ph.Ka;
+      const size_t row = rowoff(k);
+      const f32x4 vm = ld_dd1(row, om), vl = ld_dd1(row, ol), vr = ld_dd1(row, orr);
+      m = vm * splat4(rok ? 1.f : 0.f);
+      l = vl * splat4((rok && xl_ok) ? 1.f : 0.f);
+      rr = vr * splat4((rok && xr_ok) ? 1.f : 0.f);
+    };
+    // forward input row k at own column: raw value and validity
+    auto ld_e = [&](int k, f32x4 &raw, bool &ok) {
+      ok = active && k >= 0 && k < ph.Ka;
+      raw = ld4_su(x + rowoff(k), om);
+    };
+    auto eact = [&](f32x4 raw, bool ok) -> f32x4 {
+      const f32x4 v = dl3_act4(cn.s * raw + cn.t, act);
+      return v * splat4(ok ? 1.f : 0.f);
+    };
 
-  f32x4 accA = splat4(0.f), accB = splat4(0.f);
+    f32x4 accA = splat4(0.f), accB = splat4(0.f);
 
-  if (k0 < k1) {
-    // groups of R dY rows: the 7*R loads of a group (3 taps x {g, yraw} + the forward input row) are issued
-    // together, R x 3 of them cache-missing — twice the bytes in flight of a one-row software pipeline
-    constexpr int R = 2;
-    f32x4 e_prev = splat4(0.f), e_cur, e_next;
-    bool ok_prev = false, ok_cur, ok_next;
-    // dY row slots ks..ke (halo slots outside the phase are all-zero rows: skipped, see dw_march_fwd)
-    const bool bot_halo = k1 < Ka;
-    const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;
-    ld_e(ks, e_cur, ok_cur);
-    ld_e(ks + 1, e_next, ok_next);
-    // FAST (round 5, see dw_march_fwd): an interior group of an all-active workgroup — both dY rows live, both dx rows
-    // inside the chunk, the forward-input rows kg-1 .. kg+R+1 inside the phase — with the optional operands known at
-    // compile time (SX: sums against another tensor, ADD: residual addend): no branch around a request or a store, so
-    // the stores are counted and the group's last operands are waited for with vmcnt(1), not vmcnt(0).
-    auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {
-      constexpr bool FAST = decltype(fastc)::value, SXC = SXK, ADDC = ADDK;
-      f32x4 l[R], m[R], rr[R], e_new[R], sxv[R], addv[R];
-      bool ok_new[R];
+    if (ph.k0 < ph.k1) {
+      // groups of R dY rows: the 7*R loads of a group (3 taps x {g, yraw} + the forward input row) are issued
+      // together, R x 3 of them cache-missing — twice the bytes in flight of a one-row software pipeline
+      constexpr int R = 2;
+      f32x4 e_prev = splat4(0.f), e_cur, e_next;
+      bool ok_prev = false, ok_cur, ok_next;
+      ld_e(ph.ks, e_cur, ok_cur);
+      ld_e(ph.ks + 1, e_next, ok_next);
+      // FAST (round 5, see dw_walk): an interior group of an all-active workgroup — both dY rows live, both dx rows
+      // inside the chunk, the forward-input rows kg-1 .. kg+R+1 inside the phase — with the optional operands known at
+      // compile time (SX: sums against another tensor, ADD: residual addend): no branch around a request or a store, so
+      // the stores are counted and the group's last operands are waited for with vmcnt(1), not vmcnt(0).
+      auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(fastc)::value, SXC = SXK, ADDC = ADDK;
+        f32x4 l[R], m[R], rr[R], e_new[R], sxv[R], addv[R];
+        bool ok_new[R];
 #pragma unroll
-      for (int j = 0; j < R; j++) {
-        if constexpr (FAST) {
-          const size_t row = nimg + (size_t)(a + (kg + j) * r) * W * C;
-          m[j] = ld_dd1(row, om);
-          l[j] = ld_dd1(row, ol) * splat4(xl_ok ? 1.f : 0.f);
-          rr[j] = ld_dd1(row, orr) * splat4(xr_ok ? 1.f : 0.f);
-          ld_e(kg + j + 2, e_new[j], ok_new[j]);   // (row kg+j+2 may be the slot below the phase: clamped + flagged as ever)
-          const size_t orow = nimg + (size_t)(a + (kg + j - 1) * r) * W * C;
-          if constexpr (SXC) sxv[j] = ld4_su(sx + orow, om);
-          if constexpr (ADDC) addv[j] = ld4_su(dx_add + orow, om);
-        } else {
-          ld_dd((kg + j <= ke) ? kg + j : -1, l[j], m[j], rr[j]);
-          ld_e(kg + j + 2, e_new[j], ok_new[j]);
-          // slot j of the group finishes dx row kg + j - 1: its x_hat operand and its residual addend (own column, clamped
-          // row: always in bounds) travel with the group's requests — a load inside the predicated store block below is
-          // waited for with vmcnt(0), which the in-order counter turns into "everything this wave has in flight" (round 5)
-          const size_t orow = rowoff(kg + j - 1);
-          if constexpr (SXC) sxv[j] = ld4_su(sx + orow, om);
-          if constexpr (ADDC) addv[j] = ld4_su(dx_add + orow, om);
+        for (int j = 0; j < R; j++) {
+          if constexpr (FAST) {
+            const size_t row = nimg + (size_t)(a + (kg + j) * r) * W * C;
+            m[j] = ld_dd1(row, om);
+            l[j] = ld_dd1(row, ol) * splat4(xl_ok ? 1.f : 0.f);
+            rr[j] = ld_dd1(row, orr) * splat4(xr_ok ? 1.f : 0.f);
+            ld_e(kg + j + 2, e_new[j], ok_new[j]);   // (row kg+j+2 may be the slot below the phase: clamped + flagged as ever)
+            const size_t orow = nimg + (size_t)(a + (kg + j - 1) * r) * W * C;
+            if constexpr (SXC) sxv[j] = ld4_su(sx + orow, om);
+            if constexpr (ADDC) addv[j] = ld4_su(dx_add + orow, om);
+          } else {
+            ld_dd((kg + j <= ph.ke) ? kg + j : -1, l[j], m[j], rr[j]);
+            ld_e(kg + j + 2, e_new[j], ok_new[j]);
+            // slot j of the group finishes dx row kg + j - 1: its x_hat operand and its residual addend (own column, clamped
+            // row: always in bounds) travel with the group's requests — a load inside the predicated store block below is
+            // waited for with vmcnt(0), which the in-order counter turns into "everything this wave has in flight" (round 5)
+            const size_t orow = rowoff(kg + j - 1);
+            if constexpr (SXC) sxv[j] = ld4_su(sx + orow, om);
+            if constexpr (ADDC) addv[j] = ld4_su(dx_add + orow, om);
+          }
         }
-      }
 #pragma unroll
-      for (int j = 0; j < R; j++) {
-        const int k = kg + j;
-        const bool kv = FAST || k <= ke;   // (predicated, not `break`: see dw_march_fwd)
-        if (FAST || (k >= k0 && k < k1)) {
-          // dW[i][j] += T(x)[k+i-1][x] * dY[k][x-(j-1)r] : j=0 -> right tap, j=2 -> left tap
-          f32x4 ea0 = eact(e_prev, ok_prev), ea1 = eact(e_cur, ok_cur), ea2 = eact(e_next, ok_next);
-          dwv[0] += ea0 * rr[j]; dwv[1] += ea0 * m[j]; dwv[2] += ea0 * l[j];
-          dwv[3] += ea1 * rr[j]; dwv[4] += ea1 * m[j]; dwv[5] += ea1 * l[j];
-          dwv[6] += ea2 * rr[j]; dwv[7] += ea2 * m[j]; dwv[8] += ea2 * l[j];
-        }
-        // dY row k feeds dx[k-1] (tap row 0), dx[k] (tap row 1), dx[k+1] (tap row 2)
-        f32x4 h0 = wv[0] * rr[j] + wv[1] * m[j] + wv[2] * l[j];
-        f32x4 h1 = wv[3] * rr[j] + wv[4] * m[j] + wv[5] * l[j];
-        f32x4 h2 = wv[6] * rr[j] + wv[7] * m[j] + wv[8] * l[j];
-        f32x4 out = accA + h0;
-        if constexpr (FAST) {
-          out = out * dl3_mask4(s * e_prev + t, act);
-          if constexpr (ADDC) out += addv[j];
-          st4_nt_su(dx + nimg + (size_t)(a + (k - 1) * r) * W * C, oo, out);
-          s1 += out;
-          s2 += out * (((SXC ? sxv[j] : e_prev) - mu) * is);
-          accA = accB + h1;
-          accB = h2;
-          e_prev = e_cur; ok_prev = ok_cur;
-          e_cur = e_next; ok_cur = ok_next;
-          e_next = e_new[j]; ok_next = ok_new[j];
-        } else {
-          if (dx && active && kv && k - 1 >= k0 && k - 1 < k1) {
-            out = out * dl3_mask4(s * e_prev + t, act);
+        for (int j = 0; j < R; j++) {
+          const int k = kg + j;
+          const bool kv = FAST || k <= ph.ke;   // (predicated, not `break`: see dw_march_fwd)
+          if (FAST || (k >= ph.k0 && k < ph.k1)) {
+            // dW[i][j] += T(x)[k+i-1][x] * dY[k][x-(j-1)r] : j=0 -> right tap, j=2 -> left tap
+            f32x4 ea0 = eact(e_prev, ok_prev), ea1 = eact(e_cur, ok_cur), ea2 = eact(e_next, ok_next);
+            dwv[0] += ea0 * rr[j]; dwv[1] += ea0 * m[j]; dwv[2] += ea0 * l[j];
+            dwv[3] += ea1 * rr[j]; dwv[4] += ea1 * m[j]; dwv[5] += ea1 * l[j];
+            dwv[6] += ea2 * rr[j]; dwv[7] += ea2 * m[j]; dwv[8] += ea2 * l[j];
+          }
+          // dY row k feeds dx[k-1] (tap row 0), dx[k] (tap row 1), dx[k+1] (tap row 2)
+          f32x4 h0 = cn.wv[0] * rr[j] + cn.wv[1] * m[j] + cn.wv[2] * l[j];
+          f32x4 h1 = cn.wv[3] * rr[j] + cn.wv[4] * m[j] + cn.wv[5] * l[j];
+          f32x4 h2 = cn.wv[6] * rr[j] + cn.wv[7] * m[j] + cn.wv[8] * l[j];
+          f32x4 out = accA + h0;
+          if constexpr (FAST) {
+            out = out * dl3_mask4(cn.s * e_prev + cn.t, act);
             if constexpr (ADDC) out += addv[j];
             st4_nt_su(dx + nimg + (size_t)(a + (k - 1) * r) * W * C, oo, out);
             s1 += out;
-            s2 += out * (((SXC ? sxv[j] : e_prev) - mu) * is);
+            s2 += out * (((SXC ? sxv[j] : e_prev) - cn.mu) * cn.is);
+            accA = accB + h1;
+            accB = h2;
+            e_prev = e_cur; ok_prev = ok_cur;
+            e_cur = e_next; ok_cur = ok_next;
+            e_next = e_new[j]; ok_next = ok_new[j];
+          } else {
+            if (dx && active && kv && k - 1 >= ph.k0 && k - 1 < ph.k1) {
+              out = out * dl3_mask4(cn.s * e_prev + cn.t, act);
+              if constexpr (ADDC) out += addv[j];
+              st4_nt_su(dx + nimg + (size_t)(a + (k - 1) * r) * W * C, oo, out);
+              s1 += out;
+              s2 += out * (((SXC ? sxv[j] : e_prev) - cn.mu) * cn.is);
+            }
+            accA = kv ? accB + h1 : accA;
+            accB = kv ? h2 : accB;
+            e_prev = kv ? e_cur : e_prev; ok_prev = kv ? ok_cur : ok_prev;
+            e_cur = kv ? e_next : e_cur; ok_cur = kv ? ok_next : ok_cur;
+            e_next = kv ? e_new[j] : e_next; ok_next = kv ? ok_new[j] : ok_next;
           }
-          accA = kv ? accB + h1 : accA;
-          accB = kv ? h2 : accB;
-          e_prev = kv ? e_cur : e_prev; ok_prev = kv ? ok_cur : ok_prev;
-          e_cur = kv ? e_next : e_cur; ok_cur = kv ? ok_next : ok_cur;
-          e_next = kv ? e_new[j] : e_next; ok_next = kv ? ok_new[j] : ok_next;
         }
+      };
+      // (dY row k1 below the chunk — the bottom halo — only finishes dx row k1-1; its dW belongs to the next chunk: the
+      // straight-line groups stop at k1 - 1)
+      dw_walk<R>(ph, allact && dx, ph.k1 - 1, group);
+      if (!ph.bot_halo && dx && active) {  // last dx row of the phase (e_prev now holds forward input row k1-1)
+        const size_t row = nimg + (size_t)(a + (ph.k1 - 1) * r) * W * C;
+        f32x4 out = accA * dl3_mask4(cn.s * e_prev + cn.t, act);
+        if constexpr (ADDK) out += ld4_su(dx_add + row, oo);
+        st4_nt_su(dx + row, oo, out);
+        s1 += out;
+        s2 += out * (((SXK ? ld4_su(sx + row, oo) : e_prev) - cn.mu) * cn.is);
       }
-    };
-    int kg = ks;
-    group(kg, std::false_type{});
-    kg += R;
-    if (allact && dx) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // (enter the straight-line loop with nothing outstanding: see dw_march_fwd)
-      // (dY row k1 below the chunk — the bottom halo — only finishes dx row k1-1; its dW belongs to the next chunk: not here)
-      for (; kg + R - 1 < k1; kg += R) group(kg, std::true_type{});
     }
-    for (; kg <= ke; kg += R) group(kg, std::false_type{});
-    if (!bot_halo && dx && active) {  // last dx row of the phase (e_prev now holds forward input row k1-1)
-      const size_t row = nimg + (size_t)(a + (k1 - 1) * r) * W * C;
-      f32x4 out = accA * dl3_mask4(s * e_prev + t, act);
-      if constexpr (ADDK) out += ld4_su(dx_add + row, oo);
-      st4_nt_su(dx + row, oo, out);
-      s1 += out;
-      s2 += out * (((SXK ? ld4_su(sx + row, oo) : e_prev) - mu) * is);
-    }
-  }
   }  // phases of this workgroup
-  const int p = (n * ny + pc) * nxseg + xs;
-  {
-    float v[36];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      v[i * 4 + 0] = dwv[i].x; v[i * 4 + 1] = dwv[i].y; v[i * 4 + 2] = dwv[i].z; v[i * 4 + 3] = dwv[i].w;
-    }
-    reduce_px<36>(v, red);
-    if (tid < 8 && c < C) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) {
-        f32x4 o = {v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
-        st4(wpart + ((size_t)p * 9 + i) * C + c, o);
-      }
-      // the partial buffers hold max(forward plan, backward plan) rows and the folds read all of them: the two-pixel
-      // forward halves nxseg and may then halve TK once more, so its plan can be the LARGER one (8 x 64 x 64 x 960 at
-      // rate 16: 128 forward rows, 96 backward) — the rows this grid does not own are zeroed here as in the forward
-      pad_w_partial(wpart, p, N * ny * nxseg, prows, C, c);
-    }
-  }
-  if (dpart) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && c < C) {
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(dpart, p, C, c, r1, r2);
-      pad_stat_partial(dpart, p, N * ny * nxseg, prows, C, c);
-    }
-  }
+  const int p = dw_tile_row(M, tile), written = M.N * M.ny * M.nxseg;
+  dw_store_wgrad(wpart, p, written, M.prows, C, c, dwv, red);
+  dw_store_stats(dpart, p, written, M.prows, C, c, s1, s2, red);
 }
 
 // ======================================================================================
@@ -613,11 +621,8 @@ __global__ __launch_bounds__(256) void dw_gather_fwd(const float *__restrict__ x
   __shared__ float red[4 * 8 * 8];
   const int tid = threadIdx.x, cq = tid & 7, pl = tid >> 3;
   const int c = blockIdx.x * 32 + cq * 4;
-  const bool cok = c < G.C;
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-#pragma unroll
-  for (int i = 0; i < 9; i++) wv[i] = cok ? ld4(w + (size_t)i * G.C + c) : splat4(0.f);
-  if (cok && sc) { s = ld4(sc + c); t = ld4(sh + c); }
+  const bool cok = c < G.C;   // (a lane beyond the channels does no work: its pixel loop is empty)
+  const DwChan cn = dw_chan(c, G.C, w, sc, sh);
   f32x4 s1 = splat4(0.f), s2 = splat4(0.f);
   const long NP = (long)G.N * G.Ho * G.Wo;
   for (long p = (long)blockIdx.y * 32 + pl; p < NP && cok; p += (long)gridDim.y * 32) {
@@ -640,20 +645,12 @@ __global__ __launch_bounds__(256) void dw_gather_fwd(const float *__restrict__ x
       }
     }
 #pragma unroll
-    for (int q = 0; q < 9; q++) acc += (wv[q] * splat4(okf[q])) * dl3_act4(s * tap[q] + t, act);
+    for (int q = 0; q < 9; q++) acc += (cn.wv[q] * splat4(okf[q])) * dl3_act4(cn.s * tap[q] + cn.t, act);
     st4_nt(y + (size_t)p * G.C + c, acc);
     s1 += acc;
     s2 += acc * acc;
   }
-  if (part) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && cok) {
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(part, blockIdx.y, G.C, c, r1, r2);
-      pad_stat_partial(part, blockIdx.y, gridDim.y, G.prows, G.C, c);
-    }
-  }
+  dw_store_stats(part, blockIdx.y, gridDim.y, G.prows, G.C, c, s1, s2, red);
 }
 
 // ======================================================================================
@@ -669,17 +666,8 @@ __global__ __launch_bounds__(256) void dw_gather_bwd(
   __shared__ float red[4 * 8 * 36];
   const int tid = threadIdx.x, cq = tid & 7, pl = tid >> 3;
   const int c = blockIdx.x * 32 + cq * 4;
-  const bool cok = c < G.C;
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-  f32x4 kA = splat4(1.f), kB = splat4(0.f), kC = splat4(0.f), mu = splat4(0.f), is = splat4(0.f);
-#pragma unroll
-  for (int i = 0; i < 9; i++) wv[i] = cok ? ld4(w + (size_t)i * G.C + c) : splat4(0.f);
-  if (cok) {
-    if (sc) { s = ld4(sc + c); t = ld4(sh + c); }
-    if (cA) { kA = ld4(cA + c); kB = ld4(cB + c); kC = ld4(cC + c); }
-    if (dpart) { mu = ld4(xmean + c); is = ld4(xinvstd + c); }
-  }
-  const bool two = (cA != nullptr);
+  const bool cok = c < G.C;   // (a lane beyond the channels does no work: its pixel loop is empty)
+  const DwChan cn = dw_chan(c, G.C, w, sc, sh, cA, cB, cC, dpart != nullptr, xmean, xinvstd);
   f32x4 dwv[9];
 #pragma unroll
   for (int i = 0; i < 9; i++) dwv[i] = splat4(0.f);
@@ -690,10 +678,10 @@ __global__ __launch_bounds__(256) void dw_gather_bwd(
     const int iy = (int)((p / G.W) % G.H);
     const int n = (int)(p / ((long)G.W * G.H));
     const f32x4 eraw = ld4(x + (size_t)p * G.C + c);
-    const f32x4 z = s * eraw + t;
+    const f32x4 z = cn.s * eraw + cn.t;
     const f32x4 ea = dl3_act4(z, act);
     f32x4 acc = splat4(0.f);
-    const float *yr = two ? yraw : g;
+    const float *yr = dw_yr(cA, yraw, g);
     f32x4 tg[9], ty_[9];
     float okf[9];
 #pragma unroll
@@ -716,8 +704,8 @@ __global__ __launch_bounds__(256) void dw_gather_bwd(
     }
 #pragma unroll
     for (int q = 0; q < 9; q++) {
-      const f32x4 dd = (kA * tg[q] + kB * ty_[q] + kC) * splat4(okf[q]);
-      acc += dd * wv[q];
+      const f32x4 dd = dw_dy(cn, tg[q], ty_[q]) * splat4(okf[q]);
+      acc += dd * cn.wv[q];
       dwv[q] += ea * dd;
     }
     if (dx) {
@@ -725,34 +713,11 @@ __global__ __launch_bounds__(256) void dw_gather_bwd(
       if (dx_add) out += ld4(dx_add + (size_t)p * G.C + c);
       st4_nt(dx + (size_t)p * G.C + c, out);
       s1 += out;
-      s2 += out * ((eraw - mu) * is);
+      s2 += out * ((eraw - cn.mu) * cn.is);
     }
   }
-  {
-    float v[36];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      v[i * 4 + 0] = dwv[i].x; v[i * 4 + 1] = dwv[i].y; v[i * 4 + 2] = dwv[i].z; v[i * 4 + 3] = dwv[i].w;
-    }
-    reduce_px<36>(v, red);
-    if (tid < 8 && cok) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) {
-        f32x4 o = {v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
-        st4(wpart + ((size_t)blockIdx.y * 9 + i) * G.C + c, o);
-      }
-      pad_w_partial(wpart, blockIdx.y, gridDim.y, G.prows, G.C, c);
-    }
-  }
-  if (dpart) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && cok) {
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(dpart, blockIdx.y, G.C, c, r1, r2);
-      pad_stat_partial(dpart, blockIdx.y, gridDim.y, G.prows, G.C, c);
-    }
-  }
+  dw_store_wgrad(wpart, blockIdx.y, gridDim.y, G.prows, G.C, c, dwv, red);
+  dw_store_stats(dpart, blockIdx.y, gridDim.y, G.prows, G.C, c, s1, s2, red);
 }
 
 // ======================================================================================
@@ -773,14 +738,8 @@ __global__ __launch_bounds__(256) void dw_s2_bwd(
   const int c = blockIdx.x * 32 + cq * 4;
   const bool cok = c < G.C;
   const int cc = min(c, G.C - 4);
-  f32x4 wv[9], s = splat4(1.f), t = splat4(0.f);
-  f32x4 kA = splat4(1.f), kB = splat4(0.f), kC = splat4(0.f), mu = splat4(0.f), is = splat4(0.f);
-#pragma unroll
-  for (int i = 0; i < 9; i++) wv[i] = ld4(w + (size_t)i * G.C + cc);
-  if (sc) { s = ld4(sc + cc); t = ld4(sh + cc); }
-  if (cA) { kA = ld4(cA + cc); kB = ld4(cB + cc); kC = ld4(cC + cc); }
-  if (dpart) { mu = ld4(xmean + cc); is = ld4(xinvstd + cc); }
-  const float *yr = cA ? yraw : g;
+  const DwChan cn = dw_chan(c, G.C, w, sc, sh, cA, cB, cC, dpart != nullptr, xmean, xinvstd);
+  const float *yr = dw_yr(cA, yraw, g);
   f32x4 dwv[9];
 #pragma unroll
   for (int i = 0; i < 9; i++) dwv[i] = splat4(0.f);
@@ -800,7 +759,7 @@ __global__ __launch_bounds__(256) void dw_s2_bwd(
         const int oyc = min(max(oy, 0), G.Ho - 1), oxc = min(max(ox, 0), G.Wo - 1);
         const float ok = (cok && oy == oyc && ox == oxc) ? 1.f : 0.f;
         const size_t off = (((size_t)n * G.Ho + oyc) * G.Wo + oxc) * G.C + cc;
-        dd[i][j] = (kA * ld4(g + off) + kB * ld4(yr + off) + kC) * splat4(ok);
+        dd[i][j] = dw_dy(cn, ld4(g + off), ld4(yr + off)) * splat4(ok);
       }
     // the 2x2 input pixels
     f32x4 xr[2][2], ad[2][2];
@@ -818,15 +777,15 @@ __global__ __launch_bounds__(256) void dw_s2_bwd(
         ad[i][j] = dx_add ? ld4(dx_add + poff[i][j]) : splat4(0.f);
       }
     f32x4 acc[2][2];
-    acc[0][0] = wv[0] * dd[0][0] + wv[6] * dd[1][0] + wv[2] * dd[0][1] + wv[8] * dd[1][1];
-    acc[0][1] = wv[1] * dd[0][0] + wv[7] * dd[1][0];
-    acc[1][0] = wv[3] * dd[0][0] + wv[5] * dd[0][1];
-    acc[1][1] = wv[4] * dd[0][0];
+    acc[0][0] = cn.wv[0] * dd[0][0] + cn.wv[6] * dd[1][0] + cn.wv[2] * dd[0][1] + cn.wv[8] * dd[1][1];
+    acc[0][1] = cn.wv[1] * dd[0][0] + cn.wv[7] * dd[1][0];
+    acc[1][0] = cn.wv[3] * dd[0][0] + cn.wv[5] * dd[0][1];
+    acc[1][1] = cn.wv[4] * dd[0][0];
     f32x4 ea[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int j = 0; j < 2; j++) ea[i][j] = dl3_act4(s * xr[i][j] + t, act) * splat4(pok[i][j]);
+      for (int j = 0; j < 2; j++) ea[i][j] = dl3_act4(cn.s * xr[i][j] + cn.t, act) * splat4(pok[i][j]);
     dwv[0] += ea[0][0] * dd[0][0]; dwv[6] += ea[0][0] * dd[1][0]; dwv[2] += ea[0][0] * dd[0][1]; dwv[8] += ea[0][0] * dd[1][1];
     dwv[1] += ea[0][1] * dd[0][0]; dwv[7] += ea[0][1] * dd[1][0];
     dwv[3] += ea[1][0] * dd[0][0]; dwv[5] += ea[1][0] * dd[0][1];
@@ -836,40 +795,17 @@ __global__ __launch_bounds__(256) void dw_s2_bwd(
       for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-          f32x4 out = acc[i][j] * dl3_mask4(s * xr[i][j] + t, act) + ad[i][j];
+          f32x4 out = acc[i][j] * dl3_mask4(cn.s * xr[i][j] + cn.t, act) + ad[i][j];
           if (pok[i][j] != 0.f) {
             st4_nt(dx + poff[i][j], out);
             s1 += out;
-            s2 += out * ((xr[i][j] - mu) * is);
+            s2 += out * ((xr[i][j] - cn.mu) * cn.is);
           }
         }
     }
   }
-  {
-    float v[36];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      v[i * 4 + 0] = dwv[i].x; v[i * 4 + 1] = dwv[i].y; v[i * 4 + 2] = dwv[i].z; v[i * 4 + 3] = dwv[i].w;
-    }
-    reduce_px<36>(v, red);
-    if (tid < 8 && cok) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) {
-        f32x4 o = {v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
-        st4(wpart + ((size_t)blockIdx.y * 9 + i) * G.C + c, o);
-      }
-      pad_w_partial(wpart, blockIdx.y, gridDim.y, G.prows, G.C, c);
-    }
-  }
-  if (dpart) {
-    float v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-    reduce_px<8>(v, red);
-    if (tid < 8 && cok) {
-      f32x4 r1 = {v[0], v[1], v[2], v[3]}, r2 = {v[4], v[5], v[6], v[7]};
-      write_stat_partial(dpart, blockIdx.y, G.C, c, r1, r2);
-      pad_stat_partial(dpart, blockIdx.y, gridDim.y, G.prows, G.C, c);
-    }
-  }
+  dw_store_wgrad(wpart, blockIdx.y, gridDim.y, G.prows, G.C, c, dwv, red);
+  dw_store_stats(dpart, blockIdx.y, gridDim.y, G.prows, G.C, c, s1, s2, red);
 }
 
 // ---- host-side decomposition (shared by *_partials and the launchers) -------------------
@@ -885,17 +821,6 @@ struct DwPlan {
 unsigned march_grid(const DwPlan &p, int N) {
   const long total = (long)p.nxseg * p.nslab * p.ny * N;
   return (unsigned)((total + 7) / 8 * 8);
-}
-int march_fast() {
-  // straight-line interior row groups (round 5): bit 0 one-pixel forward, bit 1 two-pixel forward, bit 2 backward.
-  // Taken where a pixel's channels are whole 128-byte lines (C % 32 == 0).  Measured at B=128 (GPU call 9, cold operands,
-  // same box; ms off -> on): backward 64x64x960 r4 1.674 -> 1.577, x576 r2 1.021 -> 0.932, x384 r2 0.802 -> 0.732, x192
-  // 0.329 -> 0.293, 256x256x32 0.926 -> 0.868, but 128x128x144 (576-byte pixels: every other 128-byte store straddles two
-  // lines) 1.356 -> 1.435; forward 256x256x32 0.467 -> 0.422, 128x128x144 0.569 -> 0.603, the 64x64 maps within noise.
-  return 7;   // (the DL3_DW_FAST bit mask of round 5's A/B is gone: all three kernels take the fast path)
-}
-int march_xcd() {
-  return 1;   // (XCD-aware workgroup order; the plain order was the round-1 A/B)
 }
 
 bool march_ok(int H, int W, int stride, int rate, int pad_t, int pad_l, int Ho, int Wo) {
@@ -986,37 +911,64 @@ static int dw_check(int N, int H, int W, int C, int stride, int rate, int Ho, in
   return DL3_OK;
 }
 
+// What a launcher (fn: its name in the messages) launches for a geometry: the kernel family, the plan of its direction,
+// the grid, and the by-value geometry argument of that family (M for the march kernels, G for the gather kernels).
+// dw_prepare reads no operand and writes nothing: the launchers call it first and check their pointers behind it.
+struct DwLaunch {
+  int im;
+  DwPlan p;
+  dim3 grid;
+  DwMarch M;
+  DwGeom G;
+};
+static int dw_prepare(const char *fn, bool bwd, int N, int H, int W, int C, int stride, int rate, int pad_t, int pad_l,
+                      int Ho, int Wo, int impl, DwLaunch &L) {
+  int rc = dw_check(N, H, W, C, stride, rate, Ho, Wo);
+  if (rc) return rc;
+  const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);
+  DL3_UNSUPPORTED(im < 0, "%s: march impl needs stride 1, pad == rate, Ho == H, Wo == W", fn);
+  DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),
+                  "%s: DL3_IMPL_AUTO sizes the partials of a stride-1 Ho == H, Wo == W geometry for the march kernels, "
+                  "pad (%d,%d) != rate %d needs the gather kernels: size and launch with DL3_IMPL_GATHER", fn, pad_t, pad_l, rate);
+  const DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, bwd);
+  // the caller sized the partial buffers with dl3_dwconv3x3_partials (the larger of the forward and the backward
+  // decomposition — either can be the larger one): the kernels zero the rows nobody owns (pad_stat_partial)
+  const int Pmax = dl3_dwconv3x3_partials(N, H, W, C, stride, rate, Ho, Wo, im);
+  L.im = im;
+  L.p = p;
+  if (im == DL3_IMPL_MARCH) {
+    // straight-line interior row groups (round 5, dw_walk), in all three march kernels: taken where a pixel's channels are
+    // whole 128-byte lines.  Measured at B=128 (GPU call 9, cold operands, same box; ms off -> on): backward 64x64x960 r4
+    // 1.674 -> 1.577, x576 r2 1.021 -> 0.932, x384 r2 0.802 -> 0.732, x192 0.329 -> 0.293, 256x256x32 0.926 -> 0.868, but
+    // 128x128x144 (576-byte pixels: every other 128-byte store straddles two lines) 1.356 -> 1.435; forward 256x256x32
+    // 0.467 -> 0.422, 128x128x144 0.569 -> 0.603, the 64x64 maps within noise.
+    const int fast = (C % 32 == 0);
+    L.grid = dim3(march_grid(p, N));
+    L.M = DwMarch{H, W, C, rate, p.nchunk, p.TK, p.nxseg, p.nphase, p.ppb, p.nslab, p.ny, N, Pmax, fast};
+  } else {
+    L.grid = dim3(p.nslab, p.PB);
+    L.G = DwGeom{N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo, Pmax};
+  }
+  return DL3_OK;
+}
+
 extern "C" int dl3_dwconv3x3_fwd(const float *x, const float *in_scale, const float *in_shift, int in_act,
                                  const float *w, float *y, int N, int H, int W, int C, int stride, int rate,
                                  int pad_t, int pad_l, int Ho, int Wo, float *stat_partial, int impl,
                                  void *stream) {
-  int rc = dw_check(N, H, W, C, stride, rate, Ho, Wo);
+  DwLaunch L;
+  int rc = dw_prepare("dwconv3x3_fwd", false, N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo, impl, L);
   if (rc) return rc;
   DL3_CHECK_ARG(x && w && y, "dwconv3x3_fwd: null pointer");
   DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "dwconv3x3_fwd: scale/shift must come together");
-  const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);
-  DL3_UNSUPPORTED(im < 0, "dwconv3x3_fwd: march impl needs stride 1, pad == rate, Ho == H, Wo == W");
-  DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),
-                  "dwconv3x3_fwd: DL3_IMPL_AUTO sizes the partials of a stride-1 Ho == H, Wo == W geometry for the march kernels, "
-                  "pad (%d,%d) != rate %d needs the gather kernels: size and launch with DL3_IMPL_GATHER", pad_t, pad_l, rate);
-  DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, false);
   hipStream_t st = (hipStream_t)stream;
-  // the caller sized the partial buffer with dl3_dwconv3x3_partials (the larger of the forward and the backward
-  // decomposition — either can be the larger one): the kernels zero the rows nobody owns
-  const int Pmax = dl3_dwconv3x3_partials(N, H, W, C, stride, rate, Ho, Wo, im);
-  if (im == DL3_IMPL_MARCH) {
-    dim3 grid(march_grid(p, N));
-    if (p.two)
-      hipLaunchKernelGGL(dw_march2_fwd, grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, H, W, C, rate,
-                         p.nchunk, p.TK, p.nxseg, p.nphase, p.ppb, p.nslab, p.ny, N, march_xcd(), stat_partial, Pmax, (C % 32 == 0) ? (march_fast() & 2) : 0);
+  if (L.im == DL3_IMPL_MARCH) {
+    if (L.p.two)
+      hipLaunchKernelGGL(dw_march2_fwd, L.grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, L.M, stat_partial);
     else
-      hipLaunchKernelGGL(dw_march_fwd, grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, H, W, C, rate,
-                         p.nchunk, p.TK, p.nxseg, p.nphase, p.ppb, p.nslab, p.ny, N, march_xcd(), stat_partial, Pmax, (C % 32 == 0) ? (march_fast() & 1) : 0);
+      hipLaunchKernelGGL(dw_march_fwd, L.grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, L.M, stat_partial);
   } else {
-    DwGeom G{N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo, Pmax};
-    dim3 grid(p.nslab, p.PB);
-    hipLaunchKernelGGL(dw_gather_fwd, grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, G,
-                       stat_partial);
+    hipLaunchKernelGGL(dw_gather_fwd, L.grid, dim3(256), 0, st, x, in_scale, in_shift, in_act, w, y, L.G, stat_partial);
   }
   DL3_LAUNCH_CHECK("dwconv3x3_fwd");
   return DL3_OK;
@@ -1028,41 +980,29 @@ static int dwconv3x3_bwd_impl(const float *g, const float *yraw, const float *cA
                                  const float *x_mean, const float *x_invstd, float *dstat_partial,
                                  float *dw_partial, int N, int H, int W, int C, int stride, int rate, int pad_t,
                                  int pad_l, int Ho, int Wo, int impl, const float *stat_x, void *stream) {
-  int rc = dw_check(N, H, W, C, stride, rate, Ho, Wo);
+  DwLaunch L;
+  int rc = dw_prepare("dwconv3x3_bwd", true, N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo, impl, L);
   if (rc) return rc;
   DL3_CHECK_ARG(!stat_x || dstat_partial, "dwconv3x3_bwd_sx: stat_x without dstat_partial");
   DL3_CHECK_ARG(g && x && w && dw_partial, "dwconv3x3_bwd: null pointer");
   DL3_CHECK_ARG(!cA || (yraw && cB && cC), "dwconv3x3_bwd: cA needs yraw, cB, cC");
   DL3_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "dwconv3x3_bwd: scale/shift must come together");
   DL3_CHECK_ARG(!dstat_partial || (dx && x_mean && x_invstd), "dwconv3x3_bwd: dstat needs dx, x_mean, x_invstd");
-  const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);
-  DL3_UNSUPPORTED(im < 0, "dwconv3x3_bwd: march impl needs stride 1, pad == rate, Ho == H, Wo == W");
-  DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),
-                  "dwconv3x3_bwd: DL3_IMPL_AUTO sizes the partials of a stride-1 Ho == H, Wo == W geometry for the march kernels, "
-                  "pad (%d,%d) != rate %d needs the gather kernels: size and launch with DL3_IMPL_GATHER", pad_t, pad_l, rate);
-  DL3_UNSUPPORTED(stat_x && im != DL3_IMPL_MARCH, "dwconv3x3_bwd_sx: sums against another tensor need the march kernel (stride 1, SAME)");
-  DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, true);
+  DL3_UNSUPPORTED(stat_x && L.im != DL3_IMPL_MARCH, "dwconv3x3_bwd_sx: sums against another tensor need the march kernel (stride 1, SAME)");
   hipStream_t st = (hipStream_t)stream;
-  // (partial rows beyond this grid's: zeroed by the kernels, see pad_stat_partial)
-  const int Pmax = dl3_dwconv3x3_partials(N, H, W, C, stride, rate, Ho, Wo, im);
-  if (im == DL3_IMPL_MARCH) {
-    dim3 grid(march_grid(p, N));
-#define DL3_DW_BWD(SX_, ADD_)                                                                                              \
-  hipLaunchKernelGGL((dw_march_bwd<SX_, ADD_>), grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act, \
-                     w, dx, dx_add, x_mean, x_invstd, dstat_partial, dw_partial, H, W, C, rate, p.nchunk, p.TK, p.nxseg,    \
-                     p.nphase, p.ppb, p.nslab, p.ny, N, march_xcd(), Pmax, stat_x, (C % 32 == 0) ? (march_fast() & 4) : 0)
-    if (stat_x) { if (dx_add) DL3_DW_BWD(true, true); else DL3_DW_BWD(true, false); }
-    else { if (dx_add) DL3_DW_BWD(false, true); else DL3_DW_BWD(false, false); }
-#undef DL3_DW_BWD
+  if (L.im == DL3_IMPL_MARCH) {
+    // (what was the DL3_DW_BWD macro: only the template choice differs between the four launches)
+    auto *kernel = stat_x ? (dx_add ? dw_march_bwd<true, true> : dw_march_bwd<true, false>)
+                          : (dx_add ? dw_march_bwd<false, true> : dw_march_bwd<false, false>);
+    hipLaunchKernelGGL(kernel, L.grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act, w, dx, dx_add,
+                       x_mean, x_invstd, dstat_partial, dw_partial, L.M, stat_x);
   } else {
-    DwGeom G{N, H, W, C, stride, rate, pad_t, pad_l, Ho, Wo, Pmax};
-    dim3 grid(p.nslab, p.PB);
     if (stride == 2 && rate == 1 && pad_t <= 1 && pad_l <= 1)
-      hipLaunchKernelGGL(dw_s2_bwd, grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act, w, dx,
-                         dx_add, x_mean, x_invstd, dstat_partial, dw_partial, G);
+      hipLaunchKernelGGL(dw_s2_bwd, L.grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act, w, dx,
+                         dx_add, x_mean, x_invstd, dstat_partial, dw_partial, L.G);
     else
-      hipLaunchKernelGGL(dw_gather_bwd, grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act,
-                         w, dx, dx_add, x_mean, x_invstd, dstat_partial, dw_partial, G);
+      hipLaunchKernelGGL(dw_gather_bwd, L.grid, dim3(256), 0, st, g, yraw, cA, cB, cC, x, in_scale, in_shift, in_act,
+                         w, dx, dx_add, x_mean, x_invstd, dstat_partial, dw_partial, L.G);
   }
   DL3_LAUNCH_CHECK("dwconv3x3_bwd");
   return DL3_OK;

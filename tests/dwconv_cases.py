@@ -1,6 +1,6 @@
 """The case table of tests/test_gpu_dwconv.py (depthwise 3x3 convolutions, csrc/dwconv.hip) and what a case needs on the
-host: the planner of dwconv.hip (dw_plan, march_ok, resolve_impl, dl3_dwconv3x3_partials) and the row loops of its march
-kernels restated in Python, the branch each case was written for, and its seeded inputs (the view and the mask nudge are
+host: the planner of dwconv.hip (dw_plan, march_ok, resolve_impl, dl3_dwconv3x3_partials) and the row walk of its march
+kernels (dw_phase, dw_walk and the arguments each kernel gives dw_walk) restated in Python, the branch each case was written for, and its seeded inputs (the view and the mask nudge are
 those of tests/conv3x3_cases.py).  Importable without a GPU: tests/test_dwconv_cases_host.py checks the table here, against
 torch, against the mirror and against the text of dwconv.hip."""
 from collections import namedtuple
@@ -136,7 +136,7 @@ def fwd_kernel(case):
 
 
 def s2_dispatch(g):
-    """the condition under which dwconv3x3_bwd_impl launches dw_s2_bwd instead of dw_gather_bwd"""
+    """the condition under which dwconv3x3_bwd_impl (behind dw_prepare) launches dw_s2_bwd instead of dw_gather_bwd"""
     return g[4] == 2 and g[5] == 1 and g[6] <= 1 and g[7] <= 1
 
 
@@ -146,14 +146,15 @@ def bwd_kernel(case):
     return "dw_s2_bwd" if s2_dispatch(case.geom) else "dw_gather_bwd"
 
 
-# ---- the row loops of the march kernels, restated ----------------------------------------------------------------------------
+# ---- the row walk of the march kernels (dw_phase, dw_walk), restated ---------------------------------------------------------
 ROWS_PER_GROUP = {"dw_march_fwd": 4, "dw_march2_fwd": 3, "dw_march_bwd": 2}   # constexpr int R of each kernel
 Walk = namedtuple("Walk", "a ch rows top_halo bot_halo fast tail")
 
 
 def row_walk(g, kernel, p):
-    """per (row phase a, chunk ch) of plan p: the rows of the chunk, its halos, the number of straight-line groups an
-    all-active workgroup runs (`fast`) and of predicated groups behind them (`tail`; the first group is always predicated)"""
+    """per (row phase a, chunk ch) of plan p, as dw_phase decodes them: the rows of the chunk, its halos, the number of
+    straight-line groups dw_walk<R> runs in an all-active workgroup (`fast`) and of predicated groups behind them (`tail`; the
+    first group is always predicated)"""
     N, H, W, C, stride, r = g[:6]
     R = ROWS_PER_GROUP[kernel]
     out = []
@@ -169,12 +170,9 @@ def row_walk(g, kernel, p):
             ks = k0 - 1 if k0 > 0 else k0
             ke = k1 if bot else k1 - 1
             kg, fast, tail = ks + R, 0, 0
-            if kernel == "dw_march_bwd":
-                while kg + R - 1 < k1:
-                    fast, kg = fast + 1, kg + R
-            else:
-                while kg + R - 1 <= ke:
-                    fast, kg = fast + 1, kg + R
+            fast_last = k1 - 1 if kernel == "dw_march_bwd" else ke   # the argument each kernel gives dw_walk
+            while kg + R - 1 <= fast_last:
+                fast, kg = fast + 1, kg + R
             while kg <= ke:
                 tail, kg = tail + 1, kg + R
             out.append(Walk(a, ch, k1 - k0, k0 > 0, bot, fast, tail))
@@ -196,7 +194,7 @@ def walk_of(case, kernel):
 
 def fast_groups(case, kernel, ignore_c=False):
     """the straight-line groups `kernel` runs in the case, per all-active tile, summed over phases and chunks; 0 where the
-    launcher clears the flag (C % 32 != 0), no tile is all-active, or the backward has no dx"""
+    launchers clear the flag (dw_prepare: C % 32 != 0), no tile is all-active, or the backward has no dx"""
     g = case.geom
     if not ignore_c and (g[3] % 32 != 0 or full_tiles(g, kernel) == 0):
         return 0

@@ -169,6 +169,11 @@ def _kernel_text(src, name):
     return src[a:src.index("__global__", a)]
 
 
+def _between(src, start, end):
+    a = src.index(start)
+    return src[a:src.index(end, a + len(start))]
+
+
 def test_mirror_restates_the_source():
     """the constants and conditions the Python mirror uses are the ones csrc/dwconv.hip is written with"""
     src = re.sub(r"\s+", " ", open(HIP).read())
@@ -194,22 +199,55 @@ def test_mirror_restates_the_source():
                  "return impl == DL3_IMPL_AUTO && im == DL3_IMPL_GATHER && auto_sized_for_march(H, W, stride, Ho, Wo);",
                  "return a.P > b.P ? a.P : b.P;",
                  "if (stride == 2 && rate == 1 && pad_t <= 1 && pad_l <= 1) hipLaunchKernelGGL(dw_s2_bwd,",   # the dw_s2_bwd dispatch
-                 "const int A = (G.H + G.pad_t + 1) / 2, Bn = (G.W + G.pad_l + 1) / 2;",
-                 "(C % 32 == 0) ? (march_fast() & 1) : 0", "(C % 32 == 0) ? (march_fast() & 2) : 0",
-                 "(C % 32 == 0) ? (march_fast() & 4) : 0", "return 7;"):
+                 "const int A = (G.H + G.pad_t + 1) / 2, Bn = (G.W + G.pad_l + 1) / 2;"):
         assert text in src, text
-    assert src.count("DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),") == 2      # forward and backward
+    # the launchers: one dw_prepare holds the refusals, the plan and the `fast` flag, and every march launch takes its DwMarch
+    prepare = _between(src, "int dw_prepare(", 'extern "C"')
+    for text in ("int rc = dw_check(N, H, W, C, stride, rate, Ho, Wo);",
+                 "const int im = resolve_impl(impl, H, W, stride, rate, pad_t, pad_l, Ho, Wo);",
+                 "DL3_UNSUPPORTED(auto_mismatch(impl, im, H, W, stride, Ho, Wo),",
+                 "const DwPlan p = dw_plan(N, H, W, C, stride, rate, Ho, Wo, im, bwd);",
+                 "const int Pmax = dl3_dwconv3x3_partials(N, H, W, C, stride, rate, Ho, Wo, im);",
+                 "const int fast = (C % 32 == 0);",
+                 "L.M = DwMarch{H, W, C, rate, p.nchunk, p.TK, p.nxseg, p.nphase, p.ppb, p.nslab, p.ny, N, Pmax, fast};"):
+        assert text in prepare and src.count(text) == 1, text
+    assert src.count("DL3_UNSUPPORTED(auto_mismatch(") == 1                          # one refusal for both directions
+    assert "march_fast" not in src and "march_xcd" not in src and len(re.findall(r"\bfast = ", src)) == 1
+    assert src.count('rc = dw_prepare("dwconv3x3_fwd", false,') == 1 and src.count('rc = dw_prepare("dwconv3x3_bwd", true,') == 1
+    assert ("auto *kernel = stat_x ? (dx_add ? dw_march_bwd<true, true> : dw_march_bwd<true, false>) "
+            ": (dx_add ? dw_march_bwd<false, true> : dw_march_bwd<false, false>);") in src
+    for k in ("dw_march_fwd", "dw_march2_fwd", "kernel"):                            # `kernel`: the dw_march_bwd instantiation
+        launch = re.findall(r"hipLaunchKernelGGL\(%s, L\.grid, dim3\(256\), 0, st,[^;]*;" % k, src)
+        assert len(launch) == 1 and re.search(r", L\.M[,)]", launch[0]), k
+    assert len(re.findall(r"\bL\.M\b", src)) == 4 and src.count("DwMarch{") == 1     # filled once, launched three times
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(?dw_march", src)) == 2            # no march launch beside those
+    # the row-phase decode and the group driver, each in one place
+    phase = _between(src, "bool dw_phase(", "template <int R, class Group>")
+    for text in ("const int a = __builtin_amdgcn_readfirstlane((M.ppb > 1) ? pc * M.ppb + pi : pc / M.nchunk);",
+                 "const int ch = __builtin_amdgcn_readfirstlane((M.ppb > 1) ? 0 : pc % M.nchunk);",
+                 "const int Ka = __builtin_amdgcn_readfirstlane((a < M.H) ? (M.H - a + M.r - 1) / M.r : 0);",
+                 "const int k0 = ch * M.TK; const int k1 = min(k0 + M.TK, Ka); const int Kc = max(Ka - 1, 0);",
+                 "const bool bot_halo = k1 < Ka;",
+                 "const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;",
+                 "ph = DwPhase{a, Ka, k0, k1, Kc, bot_halo, ks, ke};", "return a < M.nphase;"):
+        assert text in phase and src.count(text) == 1, text
+    assert "int a, Ka, k0, k1, Kc; " in src and "bool bot_halo; int ks, ke; " in src   # the field order of that initialiser
+    walk = _between(src, "void dw_walk(const DwPhase &ph, bool fast_ok, int fast_last, Group &group) {", "__global__")
+    for text in ("int kg = ph.ks; group(kg, std::false_type{}); kg += R; if (fast_ok) {",
+                 "__builtin_amdgcn_s_waitcnt(0x0F70); for (; kg + R - 1 <= fast_last; kg += R) group(kg, std::true_type{}); } "
+                 "for (; kg <= ph.ke; kg += R) group(kg, std::false_type{}); }"):
+        assert text in walk, text
+    assert walk.count("group(kg, std::") == 3 and src.count("s_waitcnt(") == 1
     fwd1, fwd2, bwd = (_kernel_text(src, k) for k in ("dw_march_fwd", "dw_march2_fwd", "dw_march_bwd"))
-    for text, R, seg, loop in ((fwd1, 4, 32, "kg + R - 1 <= ke"), (fwd2, 3, 64, "kg + R - 1 <= ke"), (bwd, 2, 32, "kg + R - 1 < k1")):
+    for text, R, seg, args in ((fwd1, 4, 32, "allact, ph.ke"), (fwd2, 3, 64, "allact, ph.ke"), (bwd, 2, 32, "allact && dx, ph.k1 - 1")):
         assert text.count("constexpr int R = ") == 1 and "constexpr int R = %d;" % R in text
-        assert "for (; %s; kg += R) group(kg, std::true_type{});" % loop in text
-        assert "for (; kg <= ke; kg += R) group(kg, std::false_type{});" in text
-        assert "const bool allact = fast && (slab * 32 + 32 <= C) && (xs * %d + %d <= W);" % (seg, seg) in text
-        assert "const int ks = (k0 > 0) ? k0 - 1 : k0, ke = bot_halo ? k1 : k1 - 1;" in text and "const bool bot_halo = k1 < Ka;" in text
-        assert "const int Ka = __builtin_amdgcn_readfirstlane((a < H) ? (H - a + r - 1) / r : 0);" in text
-        assert "int kg = ks; group(kg, std::false_type{}); kg += R;" in text
+        assert text.count("dw_walk<") == 1 and "dw_walk<R>(ph, %s, group);" % args in text
+        assert "group(kg, std::" not in text and " kg += R" not in text               # no kernel drives its groups itself
+        assert "const bool allact = M.fast && (slab * 32 + 32 <= C) && (xs * %d + %d <= W);" % (seg, seg) in text
+        assert "const int H = M.H, W = M.W, C = M.C, r = M.r;" in text
+        assert "for (int pi = 0; pi < M.ppb; ++pi) {" in text and "DwPhase ph; if (!dw_phase(M, tile.pc, pi, ph)) break;" in text
+        assert "auto group = [&](int kg, auto fastc) __attribute__((always_inline)) {" in text
     assert D.ROWS_PER_GROUP == {"dw_march_fwd": 4, "dw_march2_fwd": 3, "dw_march_bwd": 2}
-    assert "if (allact && dx) {" in bwd and "if (allact) {" in fwd1 and "if (allact) {" in fwd2
     assert "const int xa = xs * 64 + (pl / r) * 2 * r + pl % r, xb = xa + r;" in fwd2
 
 

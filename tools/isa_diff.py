@@ -14,7 +14,11 @@ of both sides.  Exit status 0 whatever the verdict: the table is the result.
 Without --files-a / --files-b the output head's five files are compared file by file.  With them (either one defaults to
 the other) the kernels of all files of a side are pooled — code that moved between files — and paired by demangled name,
 template arguments kept, `(anonymous namespace)::` and the namespace of the GEMM argument structs (`pw::`) stripped; a
-kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison."""
+kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison.
+
+--memseq NAME adds, below the table, for every kernel named *NAME* that both sides have: whether the sequence of
+global_load_* / global_store_* instructions and vmcnt(N) waits in front of the kernel's first LDS or barrier instruction
+(its main loop, in layout order) is the same on both sides, and its unified diff where it is not."""
 import argparse
 import concurrent.futures as cf
 import difflib
@@ -66,6 +70,20 @@ def kernels(lines):
     return out
 
 
+def mem_sequence(stream):
+    """the global loads, global stores and vmcnt values in front of the first ds_* / s_barrier instruction"""
+    out = []
+    for l in stream:
+        op = (l.split() or [""])[0]
+        if op.startswith("ds_") or op == "s_barrier":
+            break
+        if op.startswith(("global_load", "global_store")):
+            out.append(op)
+        elif op == "s_waitcnt" and "vmcnt(" in l:
+            out.append(re.search(r"vmcnt\(\d+\)", l).group(0))
+    return out
+
+
 def demangle(names):
     """{mangled name: name the kernels are paired and shown by}"""
     try:
@@ -96,6 +114,8 @@ def main():
     ap.add_argument("--files-b", nargs="+", metavar="FILE", help="csrc/ files of tree B, pooled (default: those of --files-a)")
     ap.add_argument("-o", "--output", default=None)
     ap.add_argument("--diff", default=None, metavar="NAME", help="also print the unified diff of the kernels named *NAME*")
+    ap.add_argument("--memseq", default=None, metavar="NAME",
+                    help="below the table: the memory-request sequences of the kernels named *NAME*, one side against the other")
     a = ap.parse_args()
     # what is compared with what: the head's files one by one, or everything --files-a holds against everything --files-b holds
     groups = [(a.files_a or a.files_b, a.files_b or a.files_a)] if a.files_a or a.files_b else [([f], [f]) for f in FILES]
@@ -119,7 +139,7 @@ def main():
     rows, n_same, n_diff = [], 0, 0
     fmt = lambda s: "%6d %5d %7d %6d" % s if s else "%6s %5s %7s %6s" % ("-",) * 4
     n_a = n_b = 0
-    diffs = []
+    diffs, both = [], []
     for fa, fb in groups:
         ka, kb = pool(asm, "a", fa), pool(asm, "b", fb)
         n_a, n_b = n_a + len(ka), n_b + len(kb)
@@ -131,12 +151,21 @@ def main():
             n_diff += verdict != "identical"
             if verdict == "DIFFERENT":
                 diffs.append((n, sa[1], sb[1]))
+            if sa and sb:
+                both.append((n, sa[1], sb[1]))
             rows.append("%-12s %-44s %-9s | %s | %s" % ((sb or sa)[0], n, verdict, fmt(sa and sa[2]), fmt(sb and sb[2])))
     head = "%-12s %-44s %-9s | %6s %5s %7s %6s | %6s %5s %7s %6s" % (
         "file", "kernel", "stream", "A:inst", "vgpr", "scratch", "lds", "B:inst", "vgpr", "scratch", "lds")
     text = "\n".join(["# A = %s, B = %s; gfx950" % (a.trees[0] if a.trees else a.rev,
                                                     a.trees[1] if len(a.trees) > 1 else "the working tree"), head] + rows +
                      ["# %d kernels: %d identical, %d not; A has %d, B has %d" % (len(rows), n_same, n_diff, n_a, n_b)]) + "\n"
+    for n, sa, sb in both:
+        if a.memseq and a.memseq in n:
+            ma, mb = mem_sequence(sa), mem_sequence(sb)
+            text += "# %s: global loads / stores / vmcnt waits before the first ds_* or s_barrier: A %d, B %d, %s\n" % (
+                n, len(ma), len(mb), "the same sequence" if ma == mb else "DIFFERENT sequences")
+            if ma != mb:
+                text += "\n".join(difflib.unified_diff(ma, mb, "A " + n, "B " + n, lineterm="", n=2)) + "\n"
     sys.stdout.write(text)
     for n, sa, sb in diffs:
         if a.diff and a.diff in n:

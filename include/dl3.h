@@ -677,6 +677,37 @@ int dl3_slide_accumulate(const float *probs, float *acc, float *wsum, int Hi, in
 int dl3_slide_finalize(const float *acc, const float *wsum, float *probs_out, int *mask_out, int Hi, int Wi, int H, int W,
                        int C, int sh, int sw, int blend, void *stream);
 
+/* ---- trimap evaluation (Model.confusion_matrix_trimap): confusion matrices restricted to bands around the
+ * object boundaries — the trimap experiment of the DeepLabV3+ paper, restated with a definition of its own.
+ * labels[B][H][W]: float, 0..C-1 or void (C; every value outside 0..C-1 is read as void), as fed to the loss.
+ * Seeds of an image (a bit mask): DL3_TRIMAP_SEED_VOID — the pixel is void; DL3_TRIMAP_SEED_EDGES — some 4-neighbour inside
+ *   the same image has another label value (void counts as a value; both sides of an edge are seeds).  Images never see
+ *   each other's pixels and nothing wraps at an image border.
+ * dl3_trimap_rings: rings[b][y][x] (uint8, any alignment) = the smallest integer w >= 0 such that a seed of image b lies
+ *   within distance w, clamped to wmax + 1 ("beyond"; an image without seeds is wmax + 1 everywhere).
+ *   DL3_TRIMAP_CHEBYSHEV: distance max(|dy|, |dx|) — the (2w+1)^2 square dilation; DL3_TRIMAP_EUCLIDEAN: the smallest r
+ *   with r^2 >= min(dy^2 + dx^2), decided in integers.  workspace: dl3_trimap_workspace_bytes(B, H, W) bytes (0 for sizes
+ *   the kernels refuse), 4-byte aligned, fully overwritten.
+ * dl3_trimap_confusion: band[K+1][C][C] (int64) += 1 at [bin][t][p] for every pixel with a legal label t and a prediction
+ *   pred[b][y][x] = p in 0..C-1 (every other pixel is skipped, dl3_eval_tail_*'s confusion rule); bin = the first k with
+ *   ring <= widths[k], else K.  The bins are disjoint; their running sum over k is the confusion matrix of the band of
+ *   width widths[k], and the sum of all K + 1 the whole-image matrix.  band ACCUMULATES across calls; the caller zeroes it.
+ *   widths: a HOST pointer to K strictly increasing widths >= 1, read during the call (they go by value into the launch);
+ *   rings: dl3_trimap_rings' output for wmax >= widths[K-1].
+ * Limits: 1 <= wmax <= 254, 1 <= K <= 8, widths <= 254, 1 <= C <= 255, B, H, W >= 1, B*H*W < 2^31.  -1, and nothing is
+ * written, for a limit broken, widths not strictly increasing or < 1, an unknown metric, a seed mask outside 1..3, a null
+ * pointer or a misaligned workspace.  No allocation, no synchronisation: capturable; the only atomics are integer ones, so
+ * two runs are bit-identical. */
+#define DL3_TRIMAP_CHEBYSHEV 0
+#define DL3_TRIMAP_EUCLIDEAN 1
+#define DL3_TRIMAP_SEED_VOID 1
+#define DL3_TRIMAP_SEED_EDGES 2
+size_t dl3_trimap_workspace_bytes(int B, int H, int W);
+int dl3_trimap_rings(const float *labels, unsigned char *rings, void *workspace, int B, int H, int W, int C,
+                     int wmax, int metric, int seeds, void *stream);
+int dl3_trimap_confusion(const int *pred, const float *labels, const unsigned char *rings, long long *band,
+                         int B, int H, int W, int C, const int *widths, int K, void *stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (replaces keras.utils.multi_gpu_model, utils.py:209-211) ----
  * One process per GPU.  Rank 0 draws a 128-byte id (dl3_comm_unique_id) and hands it to the other ranks over any host
  * channel; every rank then calls dl3_comm_init with its HIP device current.  The collectives are enqueued on the

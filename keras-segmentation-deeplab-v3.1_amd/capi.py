@@ -26,6 +26,7 @@ _CTYPES = {
     "void *": ctypes.c_void_p,
     "const void *": ctypes.c_void_p,
     "const unsigned char *": ctypes.c_void_p,
+    "unsigned char *": ctypes.c_void_p,
     "void * *": ctypes.POINTER(ctypes.c_void_p),
     "const long long *": ctypes.c_void_p,
     "long long *": ctypes.c_void_p,

@@ -782,10 +782,12 @@ class Model:
                 SW = list(SW.values())[0]
             yield item[0], item[1], SW
 
-    def _evaluate_device(self, batches, confusion=None):
+    def _evaluate_device(self, batches, confusion=None, after_batch=None):
         """one evaluation pass: every batch through Engine.evaluate_batch, the results of the whole pass read once per
         engine (a ragged last batch has an engine of its own).  -> ([loss, Jaccard, accuracy] averaged over the batches
-        weighted by batch size, the per-batch triples, the batch sizes)"""
+        weighted by batch size, the per-batch triples, the batch sizes).  after_batch: callable(engine, masks) that
+        enqueues further device work on the batch's labels (engine.labels) and int32 masks [B,H,W], which stay valid
+        until the engine's next batch; the pass then runs the tail with mask=True."""
         from . import utils as U
         used, fresh = [], set()
         for xb, yb, swb in batches:
@@ -793,7 +795,10 @@ class Model:
             if id(eng) not in fresh:
                 fresh.add(id(eng))
                 eng.discard_evaluation()
-            eng.evaluate_batch(xb, yb, swb, confusion=confusion)
+            if after_batch is None:
+                eng.evaluate_batch(xb, yb, swb, confusion=confusion)
+            else:
+                after_batch(eng, eng.evaluate_batch(xb, yb, swb, confusion=confusion, mask=True))
             used.append(eng)
         if not used:
             raise ValueError("evaluation over zero batches")
@@ -829,6 +834,27 @@ class Model:
         batches = self._generator_batches(x_or_generator) if y is None else self._xy_batches(x_or_generator, y, None, batch_size)
         self._evaluate_device(batches, confusion=buf)
         return buf.cpu().numpy()
+
+    def confusion_matrix_trimap(self, x_or_generator, y=None, batch_size=32, widths=(1, 2, 4, 8, 16, 32), metric="chebyshev",
+                                seeds=("void", "edges")):
+        """Confusion matrices restricted to bands around the object boundaries (the trimap experiment of the DeepLabV3+
+        paper): int64 [K+1,C,C], CUMULATIVE — slice k is confusion_matrix() over the pixels within
+        widths[k] of a boundary seed (trimap.py: a void pixel and / or a pixel with a 4-neighbour of another label;
+        metric "chebyshev" or "euclidean"), the last slice over every pixel, equal to confusion_matrix() bit for bit.
+        One evaluation pass: behind every batch's tail, dl3_trimap_rings and dl3_trimap_confusion run on the engine's own
+        label and mask buffers; the bins accumulate on the device and cross PCIe once.  Bad arguments raise ValueError
+        before any device work.  Not part of the reference's Model API."""
+        from . import trimap
+        ws, m, s = trimap.check_widths(widths), trimap.check_metric(metric), trimap.check_seeds(seeds)
+        C = trimap.check_classes(int(self.output.shape[-1]))
+        import torch
+        band = torch.zeros(len(ws) + 1, C, C, dtype=torch.int64, device="cuda")
+
+        def after_batch(eng, masks):
+            trimap.accumulate(masks.reshape(-1), eng.labels, tuple(masks.shape), C, ws, m, s, band)
+        batches = self._generator_batches(x_or_generator) if y is None else self._xy_batches(x_or_generator, y, None, batch_size)
+        self._evaluate_device(batches, after_batch=after_batch)
+        return trimap.cumulative(band).cpu().numpy()
 
     _KNOWN_METRICS = ("Jaccard", "sparse_accuracy_ignoring_last_label")
 

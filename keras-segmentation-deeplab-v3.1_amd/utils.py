@@ -221,6 +221,74 @@ def calculate_iou_sliding(model, X, label, nb_classes=21, **slide_kwargs):
     return np.roll(plain, -1, axis=(0, 1)).astype(float)
 
 
+def iou_from_confusion(conf):
+    """(per-class IoU, their mean over the classes that occur) of a confusion matrix [C,C] in the PLAIN layout (row = label,
+    column = prediction — Model.confusion_matrix's, not calculate_iou's rolled one): I = diagonal, U = row sum + column sum
+    - I, the `I/U` notebook cell 10 computes; NaN where the union is 0, and such classes stay out of the mean (NaN if none
+    is left).  Leading axes are kept: [K+1,C,C] -> ([K+1,C], [K+1])."""
+    conf = np.asarray(conf, np.float64)
+    if conf.ndim < 2 or conf.shape[-1] != conf.shape[-2]:
+        raise ValueError("iou_from_confusion: conf must be [...,C,C], got shape %r" % (conf.shape,))
+    inter = np.diagonal(conf, axis1=-2, axis2=-1)
+    union = conf.sum(-1) + conf.sum(-2) - inter
+    iou = np.full(inter.shape, np.nan)
+    np.divide(inter, union, out=iou, where=union > 0)
+    n = (union > 0).sum(-1)
+    mean = np.full(n.shape, np.nan)
+    np.divide(np.where(union > 0, iou, 0.0).sum(-1), n, out=mean, where=n > 0)
+    return iou, (float(mean) if mean.ndim == 0 else mean)
+
+
+def _trimap_result(widths, band):
+    from . import trimap
+    conf = trimap.cumulative(band).cpu().numpy() if hasattr(band, "data_ptr") else np.asarray(band)
+    return dict(widths=tuple(widths), confusion=conf, miou=np.asarray(iou_from_confusion(conf)[1], np.float64))
+
+
+def trimap_iou(model, X, label, nb_classes=21, widths=(1, 2, 4, 8, 16, 32), metric="chebyshev", seeds=("void", "edges"),
+               crf=False, crf_unary="labels", batch_size=32):
+    """The trimap experiment: mIoU restricted to bands around the object boundaries, where the output heads
+    and the dense CRF differ.  X [N,H,W,3] raw 0-255 images, label [N,H,W] with void >= nb_classes (255 in VOC).
+    -> dict(widths, confusion = int64 [K+1,C,C] CUMULATIVE plain-layout matrices, slice k over the pixels within widths[k]
+    of a boundary and the last slice over every pixel, miou = [K+1], iou_from_confusion's mean of each slice).
+    crf=False: Model.confusion_matrix_trimap — one device evaluation pass; crf=True: the masks of
+    Model.predict_mask(crf=True, crf_unary=...) judged by trimap.band_confusion."""
+    from . import trimap
+    ws = trimap.check_widths(widths)
+    trimap.check_metric(metric), trimap.check_seeds(seeds)
+    C = int(model.output.shape[-1])
+    label = np.asarray(label)
+    lab = np.where((label >= 0) & (label < min(nb_classes, C)), label, C).astype(np.float32)
+    if not crf:
+        conf = model.confusion_matrix_trimap(X, lab.reshape(len(lab), -1, 1), batch_size=batch_size, widths=ws, metric=metric,
+                                             seeds=seeds)
+        return _trimap_result(ws, conf)
+    masks = model.predict_mask(X, batch_size=batch_size, crf=True, crf_unary=crf_unary)
+    return _trimap_result(ws, trimap.band_confusion(masks, lab, C, ws, metric=metric, seeds=seeds))
+
+
+def trimap_iou_from_masks(masks, label, nb_classes=21, widths=(1, 2, 4, 8, 16, 32), metric="chebyshev",
+                          seeds=("void", "edges")):
+    """trimap_iou for masks from anywhere (Model.predict_multiscale(output="mask"), Model.predict_sliding, a file):
+    masks and label are arrays [N,H,W] or lists of [Hi,Wi] maps of different sizes; the images of one size share one
+    launch pair, the bins of all sizes accumulate in one device array.  Labels outside 0..nb_classes-1 are void."""
+    from . import trimap
+    ws, C = trimap.check_widths(widths), trimap.check_classes(nb_classes)
+    trimap.check_metric(metric), trimap.check_seeds(seeds)
+    if len(masks) != len(label) or len(masks) == 0 or any(np.shape(m) != np.shape(l) or np.ndim(m) != 2
+                                                          for m, l in zip(masks, label)):
+        raise ValueError("trimap_iou_from_masks: masks and label must hold one [Hi,Wi] map per image, of equal shapes")
+    by_size = {}
+    for i, m in enumerate(masks):
+        by_size.setdefault(tuple(np.shape(m)), []).append(i)
+    band = None
+    for idx in by_size.values():
+        m = np.stack([np.asarray(masks[i]) for i in idx])
+        l = np.stack([np.asarray(label[i]) for i in idx])
+        band = trimap.band_confusion(m, l, C, ws, metric=metric, seeds=seeds, out=band)
+    return _trimap_result(ws, band)
+
+
 def prepare_targets(labels, n_classes=21):
     """Device-side label half of SegmentationGenerator.__getitem__ (utils.py:375-402): raw label maps
     [B,H,W] or [B,HW] (uint8 / int32; numpy array or cuda tensor) -> (Y [B,HW,1], SW [B,HW]) cuda float32 tensors, ready

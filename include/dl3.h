@@ -427,6 +427,31 @@ int dl3_softmax_xent_jaccard(const float *logits, const float *labels, const flo
 int dl3_upsample_softmax_xent_jaccard(const float *logits_lo, const float *labels, const float *weights, const float *nnz,
                                       const float *coef, float lambda, float *dlogits, float *loss_partial, int N, int Hi,
                                       int Wi, int Ho, int Wo, int C, void *stream);
+/* ---- focal loss in every form of the training loss tail (csrc/focal.hip; Lin et al. 2017 eq. 5 in softmax
+ * form, our own statement).  Inputs as the four loss kernels above take them (label outside 0..C-1: void; weights
+ * nullable: w = 1, forced to 0 on void pixels; *nnz floored as there), plus
+ *   alpha  device pointer to C floats >= 0, or NULL (every class 1); read once per workgroup into LDS
+ *   gamma  >= 0 and finite, a launch argument (-1 otherwise, nothing is written)
+ * With p = softmax(z), q = clip(p_t / sum_c p_c, 1e-7f, 1 - 1e-7f) and inside = (the unclipped quotient lies in that
+ * interval), per pixel
+ *   l = alpha[t] (1 - q)^gamma (-log q);   loss = sum_m w l / nnz
+ *   dlogits[m,k] = (w / nnz) inside alpha[t] mu (p_k - [k = t]),  mu = (1 - q)^gamma + gamma q (1 - q)^(gamma-1) (-log q)
+ * 1 - q is formed without cancellation (above one half: the renormalised sum of the other classes' probabilities) and
+ * clipped to the same interval.  gamma = 0 with alpha NULL (or all ones) is the cross-entropy: the gradient of each
+ * entry point is then its counterpart's bit for bit.  Each entry point keeps its counterpart's grid, loss partials
+ * (dl3_rows_partials, dl3_xent_fold_partials, dl3_shuffle_xent_partials), layouts and summation order; none writes probs.
+ * C <= 32 (-4 above).  The fold form needs (Wo + 2*Wi)*C*4 + 8*Wo + 128 <= 64 KB of LDS (the row, its source rows, the
+ * lerp table and alpha).  No atomics: two runs are bit-identical. */
+int dl3_focal_xent(const float *logits, const float *labels, const float *weights, const float *nnz, const float *alpha,
+                   float gamma, float *dlogits, float *loss_partial, int M, int C, void *stream);
+int dl3_upsample_focal_xent(const float *logits_lo, const float *labels, const float *weights, const float *nnz,
+                            const float *alpha, float gamma, float *dlogits, float *loss_partial, int N, int Hi, int Wi,
+                            int Ho, int Wo, int C, void *stream);
+int dl3_upsample_focal_xent_fold(const float *logits_lo, const float *labels, const float *weights, const float *nnz,
+                                 const float *alpha, float gamma, float *dlogits_xfold, float *loss_partial, int N, int Hi,
+                                 int Wi, int Ho, int Wo, int C, void *stream);
+int dl3_shuffle_focal_xent(const float *u, const float *labels, const float *weights, const float *nnz, const float *alpha,
+                           float gamma, float *du, float *loss_partial, int N, int H, int W, int C, int r, void *stream);
 /* out[i] = sum_p partial[p][i]  (fixed order) */
 int dl3_reduce_partials(const float *partial, int P, int n, float *out, void *stream);
 /* m folds in one launch, each bit-identical to its own dl3_reduce_partials call.  desc (device, int64 [m][5]): partial

@@ -1,6 +1,6 @@
 // tailmath.h — the per-pixel arithmetic the output head's consumers share (device helpers only): misc.hip (resize and the
 // training loss tails), evaltail.hip (evaluation tail), crfunary.hip (CRF unary), mine.hip and jaccard.hip (the fronts of the
-// mined and the soft-Jaccard loss) decode the same class scores.
+// mined and the soft-Jaccard loss) and focal.hip (the focal loss tails) decode the same class scores.
 #pragma once
 #include "common.h"
 
@@ -187,6 +187,49 @@ __device__ __forceinline__ float xent_pixel(float (&z)[MAXC], int C, float ssum,
     lsum += -logf(q) * w * inv_nnz;
   }
   return w * inv_nnz * inside;
+}
+
+// The focal loss of one pixel, xent_pixel with two more factors: with q the clipped renormalised
+// probability of the label and nl = -log q, the pixel adds w * at * (1 - q)^gamma * nl / nnz to lsum and scales (p - onehot)
+// by w / nnz * inside * at * mu, mu = (1 - q)^gamma + gamma q (1 - q)^(gamma - 1) nl.  at is alpha at the label (1 where
+// there is no alpha: the caller reads it, from LDS), gamma >= 0 is uniform over the launch.  With gamma = 0 and at = 1 both
+// factors are exactly 1.f and the pixel is xent_pixel's, operation for operation.
+//   1 - q   cancels where q -> 1: above one half it is the renormalised sum of the OTHER classes' probabilities (a sum of
+//           positive terms, relative error of a few ulp), below it the subtraction (an absolute error of half an ulp of 1);
+//           clipped to the interval q is clipped to, so (1 - q)^(gamma - 1) stays finite for gamma < 1
+//   x^gamma multiplications for gamma in {0, 1, 2, 3, 4}, powf otherwise; x^(gamma - 1) beside it (a quotient for powf)
+struct FocalPow {
+  float pw, pw1;   // x^gamma, x^(gamma - 1)
+};
+__device__ __forceinline__ FocalPow focal_pow(float x, float gamma) {
+  const int gi = (int)gamma;
+  if ((float)gi == gamma && gi <= 4) {   // (uniform)
+    float p1 = 1.f;
+    for (int i = 1; i < gi; i++) p1 *= x;
+    return {gi ? p1 * x : 1.f, p1};   // gamma = 0: mu's second term is 0 * p1
+  }
+  const float pw = powf(x, gamma);
+  return {pw, pw / x};
+}
+template <int MAXC>
+__device__ __forceinline__ float focal_pixel(float (&z)[MAXC], int C, float ssum, int t, float w, float inv_nnz, bool counts,
+                                             float at, float gamma, float &lsum) {
+  const ClassProbs p = class_probs<MAXC>(z, ssum, t);
+  float inside = 1.f, mod = 1.f;
+  if (counts && t >= 0 && t < C) {
+    float po = 0.f;   // the other classes (z past C - 1 is zero)
+#pragma unroll
+    for (int c = 0; c < MAXC; c++) po += (c == t) ? 0.f : z[c];
+    float q = p.pt / p.psum;
+    inside = dl3_clip_pass(q);
+    q = fminf(fmaxf(q, 1e-7f), 1.f - 1e-7f);
+    const float omq = fminf(fmaxf(q > 0.5f ? po / p.psum : 1.f - q, 1e-7f), 1.f - 1e-7f);
+    const FocalPow f = focal_pow(omq, gamma);
+    const float nl = -logf(q);
+    lsum += nl * (at * f.pw) * w * inv_nnz;
+    mod = at * (f.pw + gamma * (q * f.pw1 * nl));
+  }
+  return w * inv_nnz * inside * mod;
 }
 
 // end of a 256-thread workgroup of a loss kernel: the four waves' sums (wave_sum of the lanes' terms) in a fixed order

@@ -23,7 +23,7 @@ import torch
 
 from . import capi
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
-from .graph import check_jaccard, check_mining, raw_pixels
+from .graph import check_focal, check_jaccard, check_mining, raw_pixels
 from .head import Head
 
 _ACT = {"relu": ACT_RELU, "relu6": ACT_RELU6}
@@ -276,7 +276,7 @@ class View:
 class Engine:
     def __init__(self, model, batch, training, bn_mode="batch", dropout=True, seed=2, device=None, use_graph=True,
                  dw_impl=IMPL_AUTO, rank=None, bn_variance="keras224", external_nnz=False, opt_trainable=None, bn_update=None,
-                 mining=None, jaccard=None):
+                 mining=None, jaccard=None, focal=None):
         if not torch.cuda.is_available():
             raise capi.DL3Error("the dl3 engine needs a GPU (HIP device); there is no CPU fallback")
         self.lib = capi.lib()
@@ -308,6 +308,13 @@ class Engine:
             raise ValueError("the soft-Jaccard loss cannot ride a data-parallel (external_nnz) engine: the optimizer "
                              "finishes ONE gradient scale from the all-reduced count, and the Jaccard term has another "
                              "normaliser")
+        # focal loss: (gamma, alpha) — pixel-wise with the cross-entropy's normaliser, so it takes the
+        # place of the loss launch in whichever form the head admits and rides a data-parallel engine unchanged;
+        # None / gamma == 0 with alpha None or all ones: today's plan
+        self.focal = check_focal(focal) if training else None
+        if self.focal and (self.mining or self.jaccard):
+            raise ValueError("the focal loss, hard-example mining and the soft-Jaccard loss are separate losses and cannot "
+                             "be combined")
         self.device = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
         self.use_graph = use_graph
         self.fold_tail = True   # the loss kernel folds its gradient rows onto the low-resolution columns (the full-resolution dlogits never exist)
@@ -995,6 +1002,8 @@ class Engine:
             if not ok:
                 raise ValueError("the soft-Jaccard loss takes at most 32 classes, this head has %d" % h.v.C)
             return h if h.form == "bilinear" else h.plain
+        if self.focal and not ok:   # (§18: the forms of the cross-entropy, no generic kernel above 32 classes)
+            raise ValueError("the focal loss takes at most 32 classes, this head has %d" % h.v.C)
         if ok and h.form == "shuffle":
             ok = (os.environ.get("DL3_FUSE_SHUFFLE", "1") != "0" and h.src.buf.expected == 1 and not h.src.buf.bns
                   and self.lib.dl3_shuffle_xent_partials(*h.dims("loss")) > 0)
@@ -1054,6 +1063,20 @@ class Engine:
         return (self.mine_v.cpu().numpy(), self.mine_w.cpu().numpy(), float(self.mine_tau[0].item()),
                 int(self.mine_k[0].item()), int(ws[self.MINE_WS_COUNT]))
 
+    FOCAL_OPS = ("dl3_focal_xent", "dl3_upsample_focal_xent", "dl3_upsample_focal_xent_fold", "dl3_shuffle_focal_xent")
+
+    def _focal_args(self, C):
+        """alpha and gamma of the focal loss launch: the class weights uploaded once (a scalar broadcast; None: a null
+        pointer), gamma frozen in the launch"""
+        gamma, alpha = self.focal
+        self.focal_alpha = None
+        if alpha is not None:
+            if len(alpha) not in (1, C):
+                raise ValueError("the focal loss got %d class weights for a head of %d classes" % (len(alpha), C))
+            self.focal_alpha = self.zeros(C)
+            self.focal_alpha.copy_(torch.tensor(np.broadcast_to(np.asarray(alpha, np.float32), (C,)).copy()))
+        return dict(alpha=ptr(self.focal_alpha), gamma=gamma)
+
     JACCARD_OPS = ("dl3_jaccard_sums_plain", "dl3_jaccard_sums_bilinear", "dl3_jaccard_coef", "dl3_softmax_xent_jaccard",
                    "dl3_upsample_softmax_xent_jaccard")
 
@@ -1105,7 +1128,9 @@ class Engine:
         h = self.loss_head
         # the full-resolution gradient never exists where a row of it fits the LDS: the loss kernel folds each output row
         # onto the low-resolution columns, the resize unit's backward folds the rows
-        fold = h.form == "bilinear" and self.fold_tail and ((buf.W + 2 * h.src.buf.W) * C + 2 * buf.W) * 4 <= 65536
+        # (the focal kernel keeps alpha, 32 floats, beside the row)
+        fold = h.form == "bilinear" and self.fold_tail and (
+            ((buf.W + 2 * h.src.buf.W) * C + 2 * buf.W) * 4 + (128 if self.focal else 0) <= 65536)
         if self.jaccard:
             # the full-resolution gradient in the logits buffer, whatever the head: the resize unit's ordinary backward
             # (the phase shift's) takes it from there — no folded, no shuffle-fused form of this loss
@@ -1122,8 +1147,10 @@ class Engine:
             self.lossP = self.lib.dl3_rows_partials(M)
         if not self.jaccard:
             self.loss_part = self.zeros(self.lossP)
-            self.op(self.ops_fwd, *h.launch("loss", fold, labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz), grad=ptr(g),
-                                      part=ptr(self.loss_part)))
+            # the focal loss: the same form, grid and partials, its own entry point with alpha and gamma on top
+            family, extra = ("focal_loss", self._focal_args(C)) if self.focal else ("loss", {})
+            self.op(self.ops_fwd, *h.launch(family, fold, labels=ptr(self.labels), w=wsrc, nnz=ptr(self.nnz), grad=ptr(g),
+                                      part=ptr(self.loss_part), **extra))
             self.op(self.ops_fwd, "dl3_reduce_partials", ptr(self.loss_part), self.lossP, 1, ptr(self.loss))
         buf.done = 1
         assert buf.expected == 1

@@ -43,6 +43,32 @@ def check_jaccard(weight):
     return float(weight) or None
 
 
+def check_focal(focal):
+    """(gamma, alpha) of the focal loss -> (float gamma, tuple alpha or None), or None where the loss is off (None; gamma
+    == 0 with alpha None or all ones: the cross-entropy).  alpha: None, one number (broadcast to every class; so is a
+    one-element sequence) or one number per class.  ValueError for a gamma that is not a finite number >= 0 and for an
+    alpha entry that is not one"""
+    if focal is None:
+        return None
+    gamma, alpha = focal
+    fmax = float(np.finfo(np.float32).max)   # (the launch takes gamma as a float, the device holds alpha as floats)
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer)) and 0.0 <= float(v) <= fmax
+    if not number(gamma):
+        raise ValueError("gamma must be a finite number >= 0, got %r" % (gamma,))
+    if alpha is not None:
+        entries = [alpha] if np.ndim(alpha) == 0 else list(np.asarray(alpha, object).reshape(-1))
+        if not entries or not all(number(a) for a in entries):
+            raise ValueError("alpha must be None, a finite number >= 0 or one such number per class, got %r" % (alpha,))
+        alpha = tuple(float(a) for a in entries)
+        if all(a == 1.0 for a in alpha):
+            alpha = None
+    if float(gamma) == 0.0 and alpha is None:
+        return None
+    return float(gamma), alpha
+
+
 def raw_pixels(x):
     """raw 0-255 pixels as the package takes them: a device tensor or a uint8 array (decoded images) as it is, anything
     else as a float32 array (the reference's arrays)"""
@@ -587,16 +613,33 @@ class Model:
         loss = (getattr(self, "_compiled", None) or {}).get("loss")
         return getattr(loss, "jaccard", None)
 
+    def _focal(self):
+        """(gamma, alpha) of a compile(loss=utils.sparse_focal_crossentropy(...)) whose loss is on, else None (any other
+        loss; gamma == 0 with alpha None or all ones)"""
+        loss = (getattr(self, "_compiled", None) or {}).get("loss")
+        return getattr(loss, "focal", None)
+
     def _engine_key(self, batch, training, kw):
         """(cache key, constructor keywords) of the engine for (batch, mode, keywords): host-only.  A training engine's
-        key carries the trainable flags and, through the keywords, the mining settings or the Jaccard weight of the
-        compiled loss — a plan lowered for one setting is never replayed for another; a loss that neither mines nor adds
-        the Jaccard term adds nothing to either."""
+        key carries the trainable flags and, through the keywords, the mining settings, the Jaccard weight or the focal
+        (gamma, alpha) of the compiled loss — a plan lowered for one setting is never replayed for another; a loss that
+        neither mines nor adds the Jaccard term nor modulates adds nothing to either.  The focal loss with mining or with
+        the Jaccard term (they are separate loss objects; keywords could still ask for both) raises ValueError."""
         kw = dict(kw)
         if training and "mining" not in kw and self._mining() is not None:
             kw["mining"] = self._mining()
         if training and "jaccard" not in kw and self._jaccard() is not None:
             kw["jaccard"] = self._jaccard()
+        if training and "focal" not in kw and self._focal() is not None:
+            kw["focal"] = self._focal()
+        if "focal" in kw:   # the normal form: hashable, and absent where the loss is off (the plain key)
+            kw["focal"] = check_focal(kw["focal"]) if training else None
+            if kw["focal"] is None:
+                del kw["focal"]
+        if training and kw.get("focal") is not None and (
+                check_mining(kw.get("mining")) is not None or check_jaccard(kw.get("jaccard")) is not None):
+            raise ValueError("the focal loss, hard-example mining and the soft-Jaccard loss are separate losses and cannot "
+                             "be combined")
         key = (int(batch), bool(training), tuple(sorted(kw.items())))
         if training:
             flags = self._training_flags()

@@ -1,11 +1,13 @@
 """The output head as a kernel that reads class scores sees it.
 
 Three forms: `plain` — materialised logits; `bilinear` — the low-resolution logits in front of the final
-dl3_resize_bilinear_fwd; `shuffle` — the unshuffled Subpixel output in front of dl3_phase_shift.  Four kernel families take
-any of them; the two of the soft-Jaccard loss (§16) take `plain` and `bilinear`.  Engine._lo_softmax decides the form
+dl3_resize_bilinear_fwd; `shuffle` — the unshuffled Subpixel output in front of dl3_phase_shift.  Five kernel families take
+any of them (the focal loss, §18, in the forms of the cross-entropy it stands in for); the two of the soft-Jaccard loss
+(§16) take `plain` and `bilinear`.  Engine._lo_softmax decides the form
 once; each consumer admits it by a rule of its own or reads the same head as `plain`; KERNELS is the one place that names the entry points and their argument order."""
 
 _LOSS = ("src", "labels", "w", "nnz", "grad", "part", "dims")
+_FOCAL = ("src", "labels", "w", "nnz", "alpha", "gamma", "grad", "part")
 _EVAL = ("src", "labels", "w", "part", "loss", "nnz", "counts", "confusion", "mask")
 # family -> form -> (entry point, arguments).  A string is a value the caller names, or one of the head's dimension tuples
 # ("rows": M, C; "images": B, HW, C; "dims": the form's own); anything else is passed as it stands.
@@ -15,6 +17,11 @@ KERNELS = {
              # grad: each output row folded onto the low-resolution columns (the resize unit's backward folds the rows)
              "bilinear_fold": ("dl3_upsample_softmax_xent_fold", _LOSS),
              "shuffle": ("dl3_shuffle_softmax_xent", _LOSS)},
+    # the focal loss: the `loss` family's forms, grids and partials, alpha (device pointer or None) and gamma on top
+    "focal_loss": {"plain": ("dl3_focal_xent", _FOCAL + ("rows",)),
+                   "bilinear": ("dl3_upsample_focal_xent", _FOCAL + ("dims",)),
+                   "bilinear_fold": ("dl3_upsample_focal_xent_fold", _FOCAL + ("dims",)),
+                   "shuffle": ("dl3_shuffle_focal_xent", _FOCAL + ("dims",))},
     "pixel_xent": {"plain": ("dl3_pixel_xent_plain", ("src", "labels", "w", "out", "rows")),
                    "bilinear": ("dl3_pixel_xent_bilinear", ("src", "labels", "w", "out", "dims")),
                    "shuffle": ("dl3_pixel_xent_shuffle", ("src", "labels", "w", "out", "dims"))},

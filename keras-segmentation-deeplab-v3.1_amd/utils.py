@@ -128,6 +128,46 @@ class sparse_crossentropy_jaccard:
         return "sparse_crossentropy_jaccard(%r)" % (self.jaccard_weight,)
 
 
+class sparse_focal_crossentropy:
+    """Loss object for Model.compile(loss=...): the focal loss of Lin et al. 2017 (eq. 5) in softmax form with fixed
+    per-class weights, evaluated on the device in every form of the training loss tail.  With p the
+    softmax, q = clip(p_t / sum p, 1e-7, 1 - 1e-7) as sparse_crossentropy_ignoring_last_label forms it and t the label, a
+    pixel's loss is alpha[t] * (1 - q)**gamma * -log(q); the step loss weights it with the sample weight and divides by
+    count(sample weight != 0), as the cross-entropy.  alpha: None (every class 1), one number (every class) or one number
+    per class.  gamma = 0 with alpha None or all ones switches the loss off (the plain loss, bit for bit).  Calling the
+    object on host arrays returns the per-pixel FOCAL loss in float64 (the siblings return the cross-entropy: here the
+    per-pixel loss is the focal one).  Evaluation and prediction do not see it: val_loss stays the cross-entropy.  Trains
+    under Model.distribute(); not available together with hard-example mining or the soft-Jaccard term."""
+
+    def __init__(self, gamma=2.0, alpha=None):
+        G.check_focal((gamma, alpha))   # ValueError
+        self.gamma = float(gamma)
+        self.alpha = None if alpha is None else (float(alpha) if np.ndim(alpha) == 0 else tuple(
+            float(a) for a in np.asarray(alpha, np.float64).reshape(-1)))
+        self.__name__ = "sparse_focal_crossentropy"
+
+    @property
+    def focal(self):
+        """(gamma, alpha) for the training engine; None where the loss is off"""
+        return G.check_focal((self.gamma, self.alpha))
+
+    def __call__(self, y_true, y_pred):
+        p = np.asarray(y_pred, np.float64)
+        B, HW, C = p.shape
+        t = np.asarray(y_true).reshape(B, HW).astype(np.int64)
+        alpha = np.ones(C) if self.alpha is None else np.asarray(self.alpha, np.float64).reshape(-1)
+        if alpha.size not in (1, C):
+            raise ValueError("alpha holds %d class weights, y_pred has %d classes" % (alpha.size, C))
+        alpha = np.broadcast_to(alpha, (C,))
+        valid = (t >= 0) & (t < C)
+        tc = np.where(valid, t, 0)
+        q = np.clip(np.take_along_axis(p / p.sum(-1, keepdims=True), tc[..., None], -1)[..., 0], 1e-7, 1 - 1e-7)
+        return np.where(valid, alpha[tc] * (1.0 - q) ** self.gamma * -np.log(q), 0.0)
+
+    def __repr__(self):
+        return "sparse_focal_crossentropy(%r, %r)" % (self.gamma, self.alpha)
+
+
 def sparse_accuracy_ignoring_last_label(y_true, y_pred):
     """utils.py:132-138 on host."""
     C = y_pred.shape[-1]

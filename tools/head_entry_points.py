@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Every entry point of the output head's five files (csrc/misc.hip, evaltail.hip, crfunary.hip, mine.hip, jaccard.hip)
-through capi on fixed seeded inputs — the A/B aid of a refactor of csrc/tailmath.h.  DL3_LIBPATH selects the library.
+"""Every entry point of the output head's six files (csrc/misc.hip, evaltail.hip, crfunary.hip, mine.hip, jaccard.hip,
+focal.hip) through capi on fixed seeded inputs — the A/B aid of a refactor of csrc/tailmath.h.  DL3_LIBPATH selects the library.
 
     head_entry_points.py --dump DIR          small shapes (the operator tests'), every output to DIR/<case>.<name>.npy
     head_entry_points.py --compare DIR DIR   byte comparison of two dumps; prints what differs (CPU only)
@@ -83,10 +83,27 @@ def run_case(tag, C, Nb, Hi, Wi, Ho, Wo, Ns, H, W, r, repeat, big, out):
                 save("xent_fold.pref" + pref, xf, lpf)
             del os.environ["DL3_XENT_PREF"]
             del probs
+            # the focal loss in the same three forms (gamma = 2, one weight per class)
+            alpha = 0.5 + 1.5 * torch.rand(C, device="cuda", generator=gen)
+            keep.append(alpha)
+            call("dl3_focal_xent", ptr(full), ptr(lab), ptr(wgt), ptr(nnz), ptr(alpha), 2.0, ptr(dl), ptr(lp), M, C)
+            save("focal_xent", dl, lp)
+            call("dl3_upsample_focal_xent", ptr(src), ptr(lab), ptr(wgt), ptr(nnz), ptr(alpha), 2.0, ptr(dl), ptr(lp), *geo)
+            save("upsample_focal_xent", dl, lp)
+            for pref in ("1", "0"):
+                os.environ["DL3_XENT_PREF"] = pref
+                call("dl3_upsample_focal_xent_fold", ptr(src), ptr(lab), ptr(wgt), ptr(nnz), ptr(alpha), 2.0, ptr(xf), ptr(lpf),
+                     *geo)
+                save("focal_fold.pref" + pref, xf, lpf)
+            del os.environ["DL3_XENT_PREF"]
         else:
             du, lp = buf(src.numel()), buf(L.dl3_shuffle_xent_partials(*geo))
             call("dl3_shuffle_softmax_xent", ptr(src), ptr(lab), ptr(wgt), ptr(nnz), ptr(du), ptr(lp), *geo)
             save("shuffle_softmax_xent", du, lp)
+            alpha = 0.5 + 1.5 * torch.rand(C, device="cuda", generator=gen)
+            keep.append(alpha)
+            call("dl3_shuffle_focal_xent", ptr(src), ptr(lab), ptr(wgt), ptr(nnz), ptr(alpha), 2.0, ptr(du), ptr(lp), *geo)
+            save("shuffle_focal_xent", du, lp)
             dl = buf(M * C)
         # mining front
         v = buf(M)

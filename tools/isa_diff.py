@@ -11,7 +11,8 @@ the __hip_cuid_* symbol) and comments are dropped, function-local label numbers 
 and the streams are compared as text: identical or different, with the instruction count, VGPRs, scratch and LDS bytes
 of both sides.  Exit status 0 whatever the verdict: the table is the result.
 
-Without --files-a / --files-b the output head's five files are compared file by file.  With them (either one defaults to
+Without --files-a / --files-b the output head's six files are compared file by file (one
+that a tree does not have yet holds no kernels there).  With them (either one defaults to
 the other) the kernels of all files of a side are pooled — code that moved between files — and paired by demangled name,
 template arguments kept, `(anonymous namespace)::` and the namespace of the GEMM argument structs (`pw::`) stripped; a
 kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison.
@@ -29,7 +30,7 @@ import subprocess
 import sys
 import tempfile
 
-FILES = ["misc.hip", "evaltail.hip", "crfunary.hip", "mine.hip", "jaccard.hip"]
+FILES = ["misc.hip", "evaltail.hip", "crfunary.hip", "mine.hip", "jaccard.hip", "focal.hip"]
 CSRC = os.path.join("keras-segmentation-deeplab-v3.1_amd", "csrc")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VOLATILE = re.compile(r"^\s*\.(file|ident)\b|__hip_cuid_")
@@ -41,6 +42,8 @@ def make_var(text, name):
 
 
 def compile_asm(tree, fname, out):
+    if not os.path.exists(os.path.join(tree, CSRC, fname)):
+        return []
     mk = open(os.path.join(tree, CSRC, "Makefile")).read()
     cmd = [make_var(mk, "HIPCC")] + make_var(mk, "CXXFLAGS").split() + ["--cuda-device-only", "-S", "-o", out, fname]
     r = subprocess.run(cmd, cwd=os.path.join(tree, CSRC), stderr=subprocess.PIPE, text=True)
@@ -137,7 +140,7 @@ def main():
             subprocess.run(["git", "-C", ROOT, "worktree", "remove", "--force", made], capture_output=True)
         shutil.rmtree(tmp, ignore_errors=True)
     rows, n_same, n_diff = [], 0, 0
-    fmt = lambda s: "%6d %5d %7d %6d" % s if s else "%6s %5s %7s %6s" % ("-",) * 4
+    fmt = lambda s: "%6d %5d %7d %6d" % s if s else "%6s %5s %7s %6s" % (("-",) * 4)
     n_a = n_b = 0
     diffs, both = [], []
     for fa, fb in groups:

@@ -437,7 +437,7 @@ int dl3_upsample_softmax_xent_jaccard(const float *logits_lo, const float *label
  *   l = alpha[t] (1 - q)^gamma (-log q);   loss = sum_m w l / nnz
  *   dlogits[m,k] = (w / nnz) inside alpha[t] mu (p_k - [k = t]),  mu = (1 - q)^gamma + gamma q (1 - q)^(gamma-1) (-log q)
  * 1 - q is formed without cancellation (above one half: the renormalised sum of the other classes' probabilities) and
- * clipped to the same interval.  gamma = 0 with alpha NULL (or all ones) is the cross-entropy: the gradient of each
+ * clipped to [1 - (1 - 1e-7f), 1 - 1e-7f], the interval 1 - q has while q is in its own.  gamma = 0 with alpha NULL (or all ones) is the cross-entropy: the gradient of each
  * entry point is then its counterpart's bit for bit.  Each entry point keeps its counterpart's grid, loss partials
  * (dl3_rows_partials, dl3_xent_fold_partials, dl3_shuffle_xent_partials), layouts and summation order; none writes probs.
  * C <= 32 (-4 above).  The fold form needs (Wo + 2*Wi)*C*4 + 8*Wo + 128 <= 64 KB of LDS (the row, its source rows, the

@@ -196,7 +196,7 @@ __device__ __forceinline__ float xent_pixel(float (&z)[MAXC], int C, float ssum,
 // factors are exactly 1.f and the pixel is xent_pixel's, operation for operation.
 //   1 - q   cancels where q -> 1: above one half it is the renormalised sum of the OTHER classes' probabilities (a sum of
 //           positive terms, relative error of a few ulp), below it the subtraction (an absolute error of half an ulp of 1);
-//           clipped to the interval q is clipped to, so (1 - q)^(gamma - 1) stays finite for gamma < 1
+//           clipped to the complement of the interval q is clipped to, so (1 - q)^(gamma - 1) stays finite for gamma < 1
 //   x^gamma multiplications for gamma in {0, 1, 2, 3, 4}, powf otherwise; x^(gamma - 1) beside it (a quotient for powf)
 struct FocalPow {
   float pw, pw1;   // x^gamma, x^(gamma - 1)
@@ -223,7 +223,8 @@ __device__ __forceinline__ float focal_pixel(float (&z)[MAXC], int C, float ssum
     float q = p.pt / p.psum;
     inside = dl3_clip_pass(q);
     q = fminf(fmaxf(q, 1e-7f), 1.f - 1e-7f);
-    const float omq = fminf(fmaxf(q > 0.5f ? po / p.psum : 1.f - q, 1e-7f), 1.f - 1e-7f);
+    // (the lower bound is 1 - the upper bound of q, 2^-23: where q is clipped to 1 - 1e-7f, 1 - q is what the formula says)
+    const float omq = fminf(fmaxf(q > 0.5f ? po / p.psum : 1.f - q, 1.f - (1.f - 1e-7f)), 1.f - 1e-7f);
     const FocalPow f = focal_pow(omq, gamma);
     const float nl = -logf(q);
     lsum += nl * (at * f.pw) * w * inv_nnz;

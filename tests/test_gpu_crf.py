@@ -251,3 +251,78 @@ def test_error_reporting(L):
     assert inf(im.data_ptr(), ptr(q), 4, None, ws.numel()) == -1
     assert inf(im.data_ptr(), ptr(q), 4, par.data_ptr(), 64) == -3 and b"workspace" in L.dl3_last_error()
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------ feature dimensions, stage boundaries, 0 / 1 iterations
+def _features_d(kind, D, B, N, rng):
+    """_features at any D in 1..6: the first D of (x, y, r, g, b), and for D = 6 a sixth column of the same scale — the
+    green channel in reversed pixel order"""
+    f = _features(kind, 5, B, N, rng)
+    if D <= 5:
+        return np.ascontiguousarray(f[:, :, :D])
+    return np.ascontiguousarray(np.concatenate([f, f[:, ::-1, 3:4]], 2))
+
+
+@pytest.mark.parametrize("kind", ["noise", "smooth"])
+@pytest.mark.parametrize("D", [1, 3, 4, 6])
+def test_message_feature_dimensions_and_stage_boundaries(D, kind):
+    """dl3_crf_message dispatches crf_pair_kernel<1|2|3> on ceil(D / 2): D = 3, 4 launch <2> (nothing else does), D = 1, 3
+    take the odd-D zero fill (2 * k + 1 < D) in <1> and <2>, D = 6 fills <3>.  N sits on, one below and one above the
+    128-column LDS stage, the 256-column compensated flush and the 256-row workgroup (127..257), and on a stage boundary
+    past the first flush (385 = 3 * 128 + 1).  L in {1, 21, 32} on the same features, as test_message_against_float64:
+    the yardstick is the oracle's float32 run, the factor 2."""
+    B = 2
+    for N in (127, 128, 129, 255, 256, 257, 385):
+        rng = np.random.default_rng(1000 * D + N + B)
+        feat = _features_d(kind, D, B, N, rng)
+        assert feat.shape == (B, N, D)
+        Q = rng.random((B, N, 32)).astype(np.float32)
+        ref = [O.message(feat[b].astype(np.float64), Q[b], np.float64) for b in range(B)]
+        f32 = [O.message(feat[b], Q[b], np.float32) for b in range(B)]
+        worst = (0.0, 0.0, 0.0)
+        for Lb in (1, 21, 32):
+            got = _message(feat, np.ascontiguousarray(Q[:, :, :Lb]))
+            again = _message(feat, np.ascontiguousarray(Q[:, :, :Lb]))
+            assert np.array_equal(got.view(np.uint32), again.view(np.uint32)), (N, Lb, "two runs differ")
+            for b in range(B):
+                r = ref[b][:, :Lb]
+                scale = np.abs(r).max()
+                yard = np.abs(f32[b][:, :Lb] - r).max() / scale
+                mine = np.abs(got[b] - r).max() / scale
+                worst = max(worst, (mine / max(yard, 1e-300), mine, yard))
+                assert mine <= 2.0 * yard, (N, Lb, b, mine, yard)
+        print("crf_message D=%d N=%d B=%d %s: worst device %.3e against oracle-fp32 yardstick (1x) %.3e (ratio %.2f)" % (
+            D, N, B, kind, worst[1], worst[2], worst[0]))
+
+
+@pytest.mark.parametrize("iters", [0, 1])
+def test_inference_zero_and_one_iteration(iters):
+    """dl3_crf_inference with iters = 0 (the first update writes Q, the energy and the MAP itself: Q = softmax(-U)) and
+    iters = 1, on one 40 x 56 case against crf_oracle.inference(..., iters=): the energy and MAP rules of
+    test_inference_end_to_end_against_float64, Q under the same yardstick; where the oracle's float32 run IS its float64
+    run (iters = 0: the energy is -U) the device has to equal it bit for bit"""
+    H, W, Lb, zu = 40, 56, 4, False
+    im, mask, _ = O.structured_case(H, W, Lb, seed=100 * Lb + H)
+    colors, labels = np.unique(mask, return_inverse=True)
+    labels = labels.reshape(-1)
+    assert len(colors) == Lb
+    U32 = C.unary_from_labels(labels, Lb, U.CRF_PARAMS["gt_prob"], zu)
+    Uo = O.unary_from_labels(labels, Lb, 0.7, zu, np.float32)
+    Q64, E64, M64 = O.inference(im, Uo.astype(np.float64), iters=iters)
+    Q32, E32, M32 = O.inference(im, Uo, dtype=np.float32, iters=iters)
+    if iters == 0:
+        assert np.array_equal(E64, -Uo.astype(np.float64)) and np.array_equal(Q64, O.softmax0(-Uo.astype(np.float64)))
+    Q, E, MAP = _inference(im[None], U32[None], iters=iters)
+    for name, got, r64, r32 in (("energy", E[0], E64, E32), ("Q", Q[0], Q64, Q32)):
+        dist = float(np.abs(r32.astype(np.float64) - r64).max())
+        mine = float(np.abs(got - r64).max())
+        print("crf_inference %dx%d L=%d iters=%d: %s max-abs device %.3e, oracle-fp32 yardstick (1x) %.3e" % (
+            H, W, Lb, iters, name, mine, dist))
+        if dist == 0.0:
+            assert np.array_equal(got, r32), name
+        else:
+            assert mine <= 2.0 * dist, (name, mine, dist)
+    _map_parity("crf_inference %dx%d L=%d iters=%d" % (H, W, Lb, iters), MAP[0], E64, E32,
+                float(np.abs(E32.astype(np.float64) - E64).max()))
+    assert np.abs(Q[0].sum(0) - 1).max() < 1e-5
+    assert np.array_equal(MAP[0], E[0].argmax(0))

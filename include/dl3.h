@@ -502,6 +502,33 @@ typedef struct {
 int dl3_opt_step(float *p, const float *g, float *s0, float *s1, size_t n, int rule, const dl3_opt_hyper *hyper,
                  const float *denom, const double *sumsq, void *stream);
 
+/* ---- L2 weight regularisers: Keras kernel_regularizer=l2(l) over a flat arena ---------------------------
+ * [TF-semantics: Keras 2.2.4 keras/regularizers.py and the total loss of keras/engine/training.py, restated from memory:
+ * l2(l) on a weight w adds l * sum(w^2) to the loss, gradient 2*l*w.]
+ * The regularised part of the arena p is a table of S runs, built on the host and resident on the device (trusted here;
+ * the host builder validates it — dl3_reduce_partials_batched's desc is the precedent):
+ *   runs (int64 [S][3]): first element, length (>= 1), first tile — runs ascend and are disjoint; a TILE is up to 1024
+ *        consecutive elements of ONE run, a run of `length` has ceil(length / 1024) of them, `first tile` is the prefix
+ *        sum of the tile counts in front of the run and `tiles` the total
+ *   coef (float [S]): l >= 0, finite
+ * out (double [2], device): out[0] = sum_s coef[s] * sum_{i in run s} p[i]^2 — squares and sums in double ((double)w *
+ *   (double)w is exact); every workgroup writes ONE double partial into `workspace` (dl3_l2_penalty_workspace_bytes(tiles),
+ *   8-byte aligned) and ONE workgroup folds them in ascending order: no float atomics, two runs give the same 64 bits;
+ *   which element goes to which lane depends on the table and the grid rule (workgroup b: tiles b, b + grid, ...) only.
+ *   out[1] = out[0] rounded once to float, stored as double: a float reader and a double reader agree.
+ * g (nullable): g[i] += ((2 * coef[s]) * p[i]) / sc on the runs, sc = grad_scale, or grad_scale / max(denom[0], 1e-20)
+ *   when denom is given — dl3_opt_step's sc, so the step's later multiplication by sc returns 2*l*w (sc == 1 divides
+ *   exactly).  grad_scale must then be positive and finite.  Elements outside the runs are neither read nor written; p is
+ *   never written.  16-byte loads and stores on the runs that start 16-byte aligned in 16-byte aligned p and g, element by
+ *   element otherwise.
+ * S == 0 (tiles == 0): out = {0, 0}; coef and the workspace are not looked at and may be NULL.  Refused before any launch,
+ * nothing written: S < 0, a NULL p / out / runs, with S > 0 a NULL coef, tiles < S, out or workspace not 8-byte aligned (-1);
+ * with S > 0 a short workspace (-3, DL3_EWORKSPACE). */
+size_t dl3_l2_penalty_workspace_bytes(long long tiles);
+int dl3_l2_penalty(const float *p, float *g, const long long *runs, const float *coef, int S, long long tiles,
+                   float grad_scale, const float *denom, double *out, void *workspace, size_t workspace_bytes,
+                   void *stream);
+
 /* ---- either side of the network: targets in, metric counts out -------------------------- */
 #define DL3_LABEL_U8 0  /* cv2.imread(path, 0) label maps (utils.py:314) */
 #define DL3_LABEL_I32 1 /* label.astype('int32') (utils.py:371) */

@@ -40,6 +40,7 @@ _CTYPES = {
     "float": ctypes.c_float,
     "double": ctypes.c_double,
     "size_t": ctypes.c_size_t,
+    "long long": ctypes.c_longlong,
     "unsigned long long": ctypes.c_ulonglong,
     "void": None,
 }

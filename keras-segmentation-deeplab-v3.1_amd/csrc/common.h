@@ -120,3 +120,25 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// sum over the 256 lanes of a workgroup in a FIXED order (butterfly inside each wave, waves 0..3 added in index order);
+// valid in lane 0
+__device__ __forceinline__ double block_sum256(double v, double *sh) {
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) sh[wave] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// the second pass of such a sum, ONE workgroup: lane t adds the partials t*c .. t*c + c - 1 in index order, then the fixed
+// fold over the lanes; valid in lane 0 (P == 0: 0)
+__device__ __forceinline__ double fold_partials256(const double *__restrict__ partial, int P, double *sh) {
+  const int c = (P + 255) / 256;
+  double acc = 0.0;
+  for (int k = 0; k < c; k++) {
+    const int i = (int)threadIdx.x * c + k;
+    if (i < P) acc += partial[i];
+  }
+  return block_sum256(acc, sh);
+}

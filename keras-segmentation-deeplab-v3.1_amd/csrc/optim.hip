@@ -13,16 +13,6 @@ static inline int sumsq_blocks(size_t n) {
   return (int)b;
 }
 
-// sum over the 256 lanes of a workgroup in a FIXED order (butterfly inside each wave, waves 0..3 added in index order);
-// valid in lane 0
-__device__ __forceinline__ double block_sum256(double v, double *sh) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sh[wave] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 // pass 1: partial[block] = sum of g[i]^2 over the block's grid-stride share, accumulated in double.  Which element goes
 // to which lane depends on (n, VEC, gridDim) only, so a repeat of the launch adds the same numbers in the same order.
 template <bool VEC>
@@ -49,17 +39,11 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float *__restr
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// pass 2: ONE workgroup; lane t adds the partials t*c .. t*c + c - 1 in index order, then the fixed fold over the lanes
+// pass 2: ONE workgroup folds the partials in a fixed order (fold_partials256, common.h)
 __global__ __launch_bounds__(256) void sumsq_fold_kernel(const double *__restrict__ partial, int P,
                                                          double *__restrict__ out) {
   __shared__ double sh[4];
-  const int c = (P + 255) / 256;
-  double acc = 0.0;
-  for (int k = 0; k < c; k++) {
-    const int i = (int)threadIdx.x * c + k;
-    if (i < P) acc += partial[i];
-  }
-  const double s = block_sum256(acc, sh);
+  const double s = fold_partials256(partial, P, sh);
   if (threadIdx.x == 0) out[0] = s;
 }
 

@@ -21,7 +21,7 @@ import types
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, regularizers
 from .capi import ACT_NONE, ACT_RELU, ACT_RELU6, IMPL_AUTO, ptr
 from .graph import check_focal, check_jaccard, check_mining, raw_pixels
 from .head import Head
@@ -276,7 +276,7 @@ class View:
 class Engine:
     def __init__(self, model, batch, training, bn_mode="batch", dropout=True, seed=2, device=None, use_graph=True,
                  dw_impl=IMPL_AUTO, rank=None, bn_variance="keras224", external_nnz=False, opt_trainable=None, bn_update=None,
-                 mining=None, jaccard=None, focal=None):
+                 mining=None, jaccard=None, focal=None, l2=None):
         if not torch.cuda.is_available():
             raise capi.DL3Error("the dl3 engine needs a GPU (HIP device); there is no CPU fallback")
         self.lib = capi.lib()
@@ -315,6 +315,11 @@ class Engine:
         if self.focal and (self.mining or self.jaccard):
             raise ValueError("the focal loss, hard-example mining and the soft-Jaccard loss are separate losses and cannot "
                              "be combined")
+        # L2 weight regularisers: the table {weight name: l} Model.compile() collected, in its normal form
+        # (regularizers.normal_form); the penalty launches sit behind the captured step, in front of the clip and the
+        # update (l2_penalty).  None / empty: no launch, today's step
+        self.l2 = regularizers.normal_form(l2) if training else None
+        self._l2_eval = {}   # table -> device tables of l2_value (evaluation: value-only launches)
         self.device = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
         self.use_graph = use_graph
         self.fold_tail = True   # the loss kernel folds its gradient rows onto the low-resolution columns (the full-resolution dlogits never exist)
@@ -451,10 +456,69 @@ class Engine:
             self.sumsq_ws = torch.zeros((ws + 7) // 8, dtype=torch.float64, device=self.device)
             self.grad_sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
             self.dummy_grad = self.zeros(4096)
+            self._l2 = self._l2_tables(self.l2) if self.l2 else None
         self.sync_all_to_device()
 
     def _arena(self, kind):
         return self.params if kind == "p" else self.state
+
+    # ------------------------------------------------------------------ L2 weight regularisers
+    def _l2_tables(self, table):
+        """dl3_l2_penalty's device-resident run tables (regularizers.build_runs) over the parameter and the state arena,
+        their partial-sum workspaces and the result: out = [parameter-arena value, the same as a float, state-arena value,
+        the same as a float]; an arena without a regularised weight has no table and its value stays 0"""
+        tabs = dict(out=torch.zeros(4, dtype=torch.float64, device=self.device), arenas=[])
+        for kind in "ps":
+            runs, coef, tiles = regularizers.build_runs(self.slots, table, kind)
+            if not len(coef):
+                tabs["arenas"].append(None)
+                continue
+            ws = int(self.lib.dl3_l2_penalty_workspace_bytes(tiles))
+            tabs["arenas"].append(dict(
+                runs=torch.from_numpy(runs).to(self.device), coef=torch.from_numpy(coef).to(self.device), S=len(coef),
+                tiles=tiles, ws=torch.zeros((ws + 7) // 8, dtype=torch.float64, device=self.device)))
+        return tabs
+
+    def _l2_launch(self, tabs, grad_scale=1.0, denom=None, grads=False):
+        """the penalty launches: parameter arena first (grads: with the gradient addend onto self.grads), then the state
+        arena, whose weights the optimizer does not update — value only"""
+        stream = torch.cuda.current_stream().cuda_stream
+        for i, (a, arena) in enumerate(zip(tabs["arenas"], (self.params, self.state))):
+            if a is None:
+                continue
+            g = ptr(self.grads) if grads and i == 0 else None
+            capi.call("dl3_l2_penalty", ptr(arena), g, a["runs"].data_ptr(), a["coef"].data_ptr(), a["S"], a["tiles"],
+                      grad_scale if g else 1.0, denom if g else None, tabs["out"].data_ptr() + 16 * i, a["ws"].data_ptr(),
+                      a["ws"].numel() * 8, stream)
+
+    @staticmethod
+    def _l2_sum(out):
+        """the penalty from a host copy of `out`: parameter arena + state arena, in double"""
+        return float(out[0]) + float(out[2])
+
+    def l2_penalty(self, grad_scale=1.0):
+        """between the backward pass (and the all-reduce, where there is one) and opt_step: the penalty of the weights as
+        they are BEFORE the update, and 2*l*w onto the gradient arena, divided by the scale opt_step(grad_scale) is about
+        to multiply the arena by — on an external_nnz engine normaliser / count_all from the arena tail.  The clip that
+        follows sees the gradient of the total loss.  Nothing regularised: no launch."""
+        if not self.l2:
+            return
+        denom = None
+        if self.external_nnz:
+            grad_scale, denom = self.nnz_host, self.grads.data_ptr() + 4 * self.tail
+        self._l2_launch(self._l2, grad_scale, denom, grads=True)
+
+    def l2_value(self, table):
+        """the penalty of `table` ({weight name: l} or its normal form) at the resident weights, for evaluation: value-only
+        launches over both arenas and one read"""
+        table = regularizers.normal_form(table)
+        if not table:
+            return 0.0
+        if table not in self._l2_eval:
+            self._l2_eval[table] = self._l2_tables(table)
+        tabs = self._l2_eval[table]
+        self._l2_launch(tabs)
+        return self._l2_sum(tabs["out"].cpu())
 
     def wptr(self, name):
         kind, off, _, _, _ = self.slots[name]
@@ -1418,18 +1482,24 @@ class Engine:
 
     def loss_value(self):
         """the loss of the last step as a float (one device read): sum(l*w) / count(w != 0) — over the GLOBAL batch on a
-        data-parallel engine, from the arena tail the all-reduce summed"""
-        if not self.external_nnz:
-            return float(self.loss[0].item())
-        t = self.grads[self.tail:self.tail + 2].cpu()
-        return float(t[1]) * self.nnz_host / max(float(t[0]), 1e-20)
+        data-parallel engine, from the arena tail the all-reduce summed.  On an engine with L2 regularisers plus the penalty
+        the last l2_penalty() call wrote — the weights train_step started from; zero before the first call, and not
+        refreshed by fwd_bwd() alone — read in the same copy (the floats widen exactly) and added in double"""
+        t = self.grads[self.tail:self.tail + 2] if self.external_nnz else self.loss[0:1]
+        if self.l2:
+            t = torch.cat([t.double(), self._l2["out"]])
+        t = t.cpu()
+        data = float(t[1]) * self.nnz_host / max(float(t[0]), 1e-20) if self.external_nnz else float(t[0])
+        return data + self._l2_sum(t[-4:]) if self.l2 else data
 
     def loss_handle(self):
-        """the same without the read: a LazyLoss that fetches when (if) somebody looks at it"""
+        """the same without the read: a LazyLoss that fetches when (if) somebody looks at it (the penalty: that of the last
+        l2_penalty() call, cloned like the loss)"""
+        pen = self._l2["out"].clone() if self.l2 else None
         if not self.external_nnz:
-            return LazyLoss(self.loss[0:1].clone(), None, 1.0)
+            return LazyLoss(self.loss[0:1].clone(), None, 1.0, pen)
         t = self.grads[self.tail:self.tail + 2].clone()
-        return LazyLoss(t[1:2], t[0:1], self.nnz_host)
+        return LazyLoss(t[1:2], t[0:1], self.nnz_host, pen)
 
     def seg_counts(self, y):
         """after forward(): per-image, per-class pixel counts [B,3,C] of the argmax mask against labels y
@@ -1711,11 +1781,13 @@ class Engine:
         if self.external_nnz:
             if comm is not None:
                 comm.allreduce_grads(self.grads)
+            self.l2_penalty()
             self.opt_step(opt, norm=True)
         else:
             scale = 1.0
             if comm is not None:
                 scale = comm.allreduce_grads(self.grads)
+            self.l2_penalty(scale)
             self.opt_step(opt, scale)
         return self.loss_handle() if lazy else self.loss_value()
 
@@ -1771,17 +1843,20 @@ class GradSink:
 
 
 class LazyLoss:
-    """the loss of one step, still on the device: num [* scale / den], read (one synchronising copy) only when somebody
-    converts it — Model.fit / fit_generator collect these and read them once per epoch instead of stalling every step"""
+    """the loss of one step, still on the device: num [* scale / den] [+ the L2 penalty of the step, l2: the clone of
+    Engine._l2_tables' out], read (one synchronising copy each) only when somebody converts it — Model.fit / fit_generator
+    collect these and read them once per epoch instead of stalling every step"""
 
-    def __init__(self, num, den, scale):
-        self._num, self._den, self._scale, self._value = num, den, scale, None
+    def __init__(self, num, den, scale, l2=None):
+        self._num, self._den, self._scale, self._value, self._l2 = num, den, scale, None, l2
 
     def __float__(self):
         if self._value is None:
             n = float(self._num.cpu()[0])
             self._value = n if self._den is None else n * self._scale / max(float(self._den.cpu()[0]), 1e-20)
-            self._num = self._den = None
+            if self._l2 is not None:
+                self._value += Engine._l2_sum(self._l2.cpu())
+            self._num = self._den = self._l2 = None
         return self._value
 
     def __repr__(self):

@@ -13,6 +13,8 @@ import os
 
 import numpy as np
 
+from . import regularizers
+
 _uids = collections.defaultdict(int)
 _rng = np.random.default_rng(0)
 
@@ -212,8 +214,13 @@ class Conv2D(Layer):
     prefix = "conv2d"
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", use_bias=True, dilation_rate=(1, 1),
-                 activation=None, name=None, kernel_initializer="glorot_uniform", **kw):
+                 activation=None, name=None, kernel_initializer="glorot_uniform", kernel_regularizer=None,
+                 bias_regularizer=None, **kw):
         super().__init__(name=name)
+        # Keras' regulariser keywords (regularizers.py): plain attributes, collected at compile()
+        regularizers.take_keywords(self, kw, kernel_regularizer=kernel_regularizer, bias_regularizer=bias_regularizer)
+        if bias_regularizer is not None and not use_bias:
+            raise ValueError("%s(use_bias=False, bias_regularizer=...): the layer has no bias" % self.kind)
         k = kernel_size[0] if isinstance(kernel_size, (tuple, list)) else kernel_size
         s = strides[0] if isinstance(strides, (tuple, list)) else strides
         r = dilation_rate[0] if isinstance(dilation_rate, (tuple, list)) else dilation_rate
@@ -240,8 +247,9 @@ class DepthwiseConv2D(Layer):
     prefix = "depthwise_conv2d"
 
     def __init__(self, kernel_size, strides=(1, 1), padding="valid", use_bias=True, dilation_rate=(1, 1),
-                 activation=None, name=None, **kw):
+                 activation=None, name=None, depthwise_regularizer=None, **kw):
         super().__init__(name=name)
+        regularizers.take_keywords(self, kw, depthwise_regularizer=depthwise_regularizer)
         k = kernel_size[0] if isinstance(kernel_size, (tuple, list)) else kernel_size
         s = strides[0] if isinstance(strides, (tuple, list)) else strides
         r = dilation_rate[0] if isinstance(dilation_rate, (tuple, list)) else dilation_rate
@@ -266,8 +274,9 @@ class BatchNormalization(Layer):
     kind = "BatchNormalization"
     prefix = "batch_normalization"
 
-    def __init__(self, epsilon=1e-3, momentum=0.99, name=None, **kw):
+    def __init__(self, epsilon=1e-3, momentum=0.99, name=None, gamma_regularizer=None, beta_regularizer=None, **kw):
         super().__init__(name=name)
+        regularizers.take_keywords(self, kw, gamma_regularizer=gamma_regularizer, beta_regularizer=beta_regularizer)
         self.cfg.update(eps=float(epsilon), momentum=float(momentum))
 
     def build(self, in_shapes):
@@ -536,8 +545,12 @@ class Model:
         # beside the hyper-parameter dict, which for Adam stays the five-key dict it always was
         rule, hyper, clipnorm, clipvalue = compile_optimizer(optimizer)
         self._refuse_jaccard_dp(loss, self._dp)
+        # the regularisers in force: {weight name: l} for l > 0.  regularizers.collect raises for anything
+        # that is neither None nor this package's l2 — here, before anything of the model changes.  One set after this
+        # call takes effect at the next compile()
+        l2 = regularizers.collect(self.layers)
         self._compiled = dict(optimizer=hyper, optimizer_object=optimizer, loss=loss, metrics=metrics,
-                              sample_weight_mode=sample_weight_mode, rule=rule, clipnorm=clipnorm, clipvalue=clipvalue)
+                              sample_weight_mode=sample_weight_mode, rule=rule, clipnorm=clipnorm, clipvalue=clipvalue, l2=l2)
         # Keras 2.2.4 collects the weights the optimizer updates HERE (`_collected_trainable_weights`), and the layers'
         # update ops (BatchNormalization moving statistics) when the train function is first built — the first
         # train_on_batch / fit after compile().  `layer.trainable` flipped in between (segmentation.ipynb: compile in
@@ -624,7 +637,8 @@ class Model:
         key carries the trainable flags and, through the keywords, the mining settings, the Jaccard weight or the focal
         (gamma, alpha) of the compiled loss — a plan lowered for one setting is never replayed for another; a loss that
         neither mines nor adds the Jaccard term nor modulates adds nothing to either.  The focal loss with mining or with
-        the Jaccard term (they are separate loss objects; keywords could still ask for both) raises ValueError."""
+        the Jaccard term (they are separate loss objects; keywords could still ask for both) raises ValueError.  The L2
+        table of compile() rides as the training keyword `l2`, absent where it is empty."""
         kw = dict(kw)
         if training and "mining" not in kw and self._mining() is not None:
             kw["mining"] = self._mining()
@@ -636,6 +650,13 @@ class Model:
             kw["focal"] = check_focal(kw["focal"]) if training else None
             if kw["focal"] is None:
                 del kw["focal"]
+        # the L2 table collected at compile(), in its normal form: absent where nothing is regularised (the plain key)
+        if training and "l2" not in kw:
+            kw["l2"] = (getattr(self, "_compiled", None) or {}).get("l2")
+        if "l2" in kw:
+            kw["l2"] = regularizers.normal_form(kw["l2"]) if training else None
+            if kw["l2"] is None:
+                del kw["l2"]
         if training and kw.get("focal") is not None and (
                 check_mining(kw.get("mining")) is not None or check_jaccard(kw.get("jaccard")) is not None):
             raise ValueError("the focal loss, hard-example mining and the soft-Jaccard loss are separate losses and cannot "
@@ -785,7 +806,7 @@ class Model:
         BATCH and the call returns the average over batches weighted by batch size.  (The host path pools the counts of
         all batches before it forms the metric ratios; it stays as it is.)"""
         if device:
-            return self._evaluate_device(self._xy_batches(x, y, sample_weight, batch_size))[0]
+            return self._with_l2(self._evaluate_device(self._xy_batches(x, y, sample_weight, batch_size))[0])
         from . import utils as U
         x, y = raw_pixels(x), np.asarray(y)
         counts, num, den = [], 0.0, 0.0
@@ -805,7 +826,7 @@ class Model:
             num += float((ell * w).sum() / max((w != 0).mean(), 1e-30) / w.size) * xb.shape[0]
             den += xb.shape[0]
         counts = np.concatenate(counts, 0)
-        return [num / den, U.Jaccard_from_counts(counts), U.accuracy_from_counts(counts)]
+        return [num / den + self._l2_addend(), U.Jaccard_from_counts(counts), U.accuracy_from_counts(counts)]
 
     # -- evaluation on the device ------------------------------------------------------------------
     @staticmethod
@@ -859,11 +880,22 @@ class Model:
         a, w = np.asarray(per, np.float64), np.asarray(sizes, np.float64)
         return [float(v) for v in (a * w[:, None]).sum(0) / w.sum()], per, sizes
 
+    def _l2_addend(self):
+        """the penalty of the compiled regularisers at the current weights: the weights do not move during
+        an evaluation pass, so it is added ONCE per call, behind the batch-size-weighted average — value-only launches
+        over both arenas of the engine the pass ran on, one double read.  Nothing regularised: 0.0 and no launch."""
+        table = regularizers.normal_form((getattr(self, "_compiled", None) or {}).get("l2"))
+        return self._active.l2_value(table) if table else 0.0
+
+    def _with_l2(self, vals):
+        """[loss, Jaccard, accuracy] of an evaluation pass with the penalty on the loss; the metrics are untouched"""
+        return [vals[0] + self._l2_addend()] + list(vals[1:])
+
     def evaluate_generator(self, generator, steps=None, **kw):
         """keras Model.evaluate_generator on the device: [loss, Jaccard, sparse_accuracy_ignoring_last_label], per-batch
         values averaged with the batch sizes as weights (Keras 2.2.4 [TF-semantics, from memory])"""
         self._check_fit_kw(kw)
-        return self._evaluate_device(self._generator_batches(generator, steps))[0]
+        return self._with_l2(self._evaluate_device(self._generator_batches(generator, steps))[0])
 
     def confusion_matrix(self, x_or_generator, y=None, batch_size=32):
         """int64 [C,C], row = label, column = prediction, void labels skipped — the notebook's calculate_iou loop (cell 10)
@@ -929,7 +961,7 @@ class Model:
                 batches = self._xy_batches(validation_data[0], validation_data[1], sw, batch_size)
             else:
                 batches = self._generator_batches(validation_data, validation_steps)
-            vals = self._evaluate_device(batches)[0]
+            vals = self._with_l2(self._evaluate_device(batches)[0])
             logs = {"val_loss": vals[0]}
             for name in names:
                 logs["val_" + name] = vals[1 + self._KNOWN_METRICS.index(name)]
@@ -1153,6 +1185,7 @@ class Model:
                     # ONE all-reduce of the arena (gradients + the shard's count(w != 0) and loss sum) behind the replayed
                     # graph, the scale finished on the device (Engine.train_step does the same for host-array batches)
                     dp.allreduce_grads(eng.grads)
+                eng.l2_penalty()    # (the scale: 1, or the external_nnz engine's own)
                 eng.opt_step(opt)   # (norm defaults to the engine's external_nnz)
                 losses.append(eng.loss_handle())
                 if ses:

@@ -17,7 +17,7 @@ class Subpixel(G.Conv2D):
     prefix = "subpixel"
 
     def __init__(self, filters, kernel_size, r, padding="valid", strides=(1, 1), activation=None, use_bias=True,
-                 kernel_initializer="glorot_uniform", name=None, **kw):
+                 kernel_initializer="glorot_uniform", name=None, kernel_regularizer=None, bias_regularizer=None, **kw):
         st = strides[0] if isinstance(strides, (tuple, list)) else strides
         ks = kernel_size if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
         if int(st) != 1 or len(set(int(q) for q in ks)) != 1 or int(ks[0]) < 1:
@@ -28,8 +28,12 @@ class Subpixel(G.Conv2D):
                              % (activation,))
         if padding not in ("same", "valid"):
             raise ValueError("Subpixel: padding must be 'same' or 'valid'")
+        # the regulariser keywords of subpixel.py:53-55 go to Conv2D, which stores or refuses them; every other unknown
+        # keyword stays dropped here, as before
+        regs = {k: v for k, v in kw.items() if k.endswith("_regularizer")}
         super().__init__(r * r * filters, kernel_size, strides=strides, padding=padding, use_bias=use_bias,
-                         activation=activation, name=name)
+                         activation=activation, name=name, kernel_regularizer=kernel_regularizer,
+                         bias_regularizer=bias_regularizer, **regs)
         self.r = int(r)
         self.cfg["r"] = int(r)
         self.cfg["out_filters"] = int(filters)

@@ -23,6 +23,8 @@ from .callbacks import (Callback, EarlyStopping, History, LambdaCallback, Learni
                         ModelCheckpoint, ReduceLROnPlateau, poly_decay)
 # ... and Keras' optimizers (utils.py:16/31: `from keras.optimizers import Adam, SGD, RMSprop`)
 from .optimizers import SGD, Adam, RMSprop  # noqa: F401
+# ... and the weight regulariser (utils.py:24/:39: `from keras.regularizers import l2`)
+from .regularizers import l2  # noqa: F401
 
 
 def sparse_crossentropy_ignoring_last_label(y_true, y_pred):
@@ -327,6 +329,33 @@ def trimap_iou_from_masks(masks, label, nb_classes=21, widths=(1, 2, 4, 8, 16, 3
         l = np.stack([np.asarray(label[i]) for i in idx])
         band = trimap.band_confusion(m, l, C, ws, metric=metric, seeds=seeds, out=band)
     return _trimap_result(ws, band)
+
+
+def add_weight_decay(model, l2=4e-5, depthwise=0.0, bias=0.0, batchnorm=0.0):
+    """DeepLab's weight decay on a built model: sets `kernel_regularizer=l2(l2)` on every Conv2D / Subpixel,
+    `depthwise_regularizer=l2(depthwise)` on every DepthwiseConv2D, `bias_regularizer=l2(bias)` on every bias and
+    `gamma_regularizer` / `beta_regularizer` = l2(batchnorm) on every BatchNormalization; 0.0 REMOVES the regulariser.
+    -> the number of weights that now carry one.  Model.compile() MUST FOLLOW: the regularisers in force are collected
+    there, so a model compiled before this call trains unchanged until it is compiled again.
+    The defaults: 4e-5 on the convolution kernels is DeepLab's training recipe; none on the depthwise kernels follows the
+    MobileNet authors' advice (few parameters per filter) — both restated from memory.  Not part of the reference."""
+    from . import regularizers as R   # (the keyword `l2` shadows the imported class in here)
+
+    def reg(l):   # noqa: E741
+        r = R.l2(l)   # refuses l < 0 and non-finite l
+        return r if r.l2 > 0 else None
+    kernel, dw, b, bn = reg(l2), reg(depthwise), reg(bias), reg(batchnorm)
+    covered = 0
+    for layer in model.layers:
+        if layer.kind in ("Conv2D", "Subpixel"):
+            layer.kernel_regularizer = kernel
+            layer.bias_regularizer = b if layer.cfg["use_bias"] else None
+        elif layer.kind == "DepthwiseConv2D":
+            layer.depthwise_regularizer = dw
+        elif layer.kind == "BatchNormalization":
+            layer.gamma_regularizer = layer.beta_regularizer = bn
+        covered += sum(getattr(layer, k, None) is not None for k in R.KEYWORDS)
+    return covered
 
 
 def prepare_targets(labels, n_classes=21):

@@ -668,6 +668,8 @@ extern "C" size_t dl3_pwconv_bwd_fused_workspace(int M, int K, int N) {
   return (size_t)dl3_pwconv_bwd_fused_splits(M, K, N) * K * N * sizeof(float);
 }
 
+// (tests/test_pwconv_cases_host.py::test_universe_restates_the_launchers reads this switch as text and tests/pwconv_cases.py universe()
+// lists its instantiations: an instantiation added, dropped or renamed here is added there, with a case that reaches it)
 extern "C" int dl3_pwconv_bwd_fused(const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
                                     const float *g, int ldg, const float *yraw, int ldyraw, const float *cA,
                                     const float *cB, const float *cC, const float *wT, float *dw, float *dx, int lddx,

@@ -103,6 +103,8 @@ static int run_gemm(const char *name, const GemmArgs &A, void *stream) {
   return DL3_OK;
 }
 
+// (tools/pwplan_probe.cpp builds the GemmArgs of a forward and of a bwd-data call the way pwconv_fwd and dl3_pwconv_bwd_data below do,
+// and the xvec / dvec of the weight gradient: a change to what these functions put into a field the planner reads goes there too)
 // dl3_pwconv_fwd (add == NULL) and dl3_pwconv_fwd_add
 static int pwconv_fwd(const char *name, const float *x, int ldx, const float *in_scale, const float *in_shift, int in_act,
                       const float *w, const float *bias, float *y, int ldy, int M, int K, int N, float *stat_partial,

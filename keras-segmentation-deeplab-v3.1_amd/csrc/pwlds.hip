@@ -269,6 +269,8 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(GemmArgs P) {
 }
 }  // namespace
 
+// (tests/test_pwconv_cases_host.py::test_universe_restates_the_launchers reads this switch as text and tests/pwconv_cases.py universe()
+// lists its instantiations: an instantiation added, dropped or renamed here is added there, with a case that reaches it)
 void pw::launch_lds(const GemmArgs &A, const GemmPlan &P, void *stream) {
   const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256);
 #define DL3_GO(KERNEL_) hipLaunchKernelGGL((KERNEL_), grid, blk, P.lds, (hipStream_t)stream, A)

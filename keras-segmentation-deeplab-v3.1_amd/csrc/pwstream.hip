@@ -611,6 +611,8 @@ void *pack_scratch(size_t bytes, hipStream_t st) {
 }
 }  // namespace
 
+// (tests/test_pwconv_cases_host.py::test_universe_restates_the_launchers reads this switch as text and tests/pwconv_cases.py universe()
+// lists its instantiations: an instantiation added, dropped or renamed here is added there, with a case that reaches it)
 int pw::launch_stream(GemmArgs A, const GemmPlan &P, void *stream) {
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256);

@@ -690,6 +690,8 @@ __global__ __launch_bounds__(64 * NW) void pw_wgrad_narrow_kernel(WgradArgs P, f
 }
 }  // namespace
 
+// (tests/test_pwconv_cases_host.py::test_universe_restates_the_launchers reads this switch as text and tests/pwconv_cases.py universe()
+// lists its instantiations: an instantiation added, dropped or renamed here is added there, with a case that reaches it)
 void pw::launch_wgrad(const WgradArgs &A, const WgradPlan &P, float *cpart, void *stream) {
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256);

@@ -665,6 +665,8 @@ __global__ __launch_bounds__(64 * NW) void pw_narrowk_kernel(GemmArgs P) {
 }
 }  // namespace
 
+// (tests/test_pwconv_cases_host.py::test_universe_restates_the_launchers reads this switch as text and tests/pwconv_cases.py universe()
+// lists its instantiations: an instantiation added, dropped or renamed here is added there, with a case that reaches it)
 void pw::launch_ws(const GemmArgs &A, const GemmPlan &P, void *stream) {
   constexpr int NW = DL3_WS2_NW;
   const dim3 grid(P.grid[0], P.grid[1], P.grid[2]), blk(256), blkw(64 * NW);

@@ -708,7 +708,8 @@ def test_fill_scale_grid_stride_loop(L, n):
 def test_bn_finalize_ragged_channel_block_and_variance_clamp(L, P):
     """bn_finalize_kernel / bn_bwd_finalize_kernel fold 8 channels per workgroup: C = 21 leaves 3 lanes of the third
     workgroup without a channel (cok == false: clamped loads, no store); partial rows of ldc = 40 read from channel
-    c0 = 8; P = 1 (31 of 32 row lanes idle) and 33 (the second trip of row lane 0).  Channel 5 holds the fp32 sums of a
+    c0 = 8; P = 1 (31 of 32 row lanes idle) and 33 (the second unrolled slot of row lane 0's first trip: a trip covers
+    8 x 32 rows, test_bn_finalize_folds_every_partial_row has the second trip).  Channel 5 holds the fp32 sums of a
     constant tensor whose s2/n - mean^2 is negative in float64: the clamp gives invstd = 1/sqrt(eps), finite scale /
     shift, and moving_var moves toward 0."""
     rng = np.random.default_rng(995)
@@ -753,3 +754,83 @@ def test_bn_finalize_ragged_channel_block_and_variance_clamp(L, P):
             h = host(o)
             OO.assert_guard(h, np.arange(C))
             OO.assert_elementwise(h[:C], rb[name], np.abs(rb[name]), 1, "bn_bwd_finalize")   # one rounding, as above
+
+
+@pytest.mark.parametrize("P", [256, 257, 1250])
+def test_bn_finalize_folds_every_partial_row(L, P):
+    """fold2 adds FOLD_U x 32 = 256 partial rows per trip: P = 256 fills the first trip exactly, 257 starts the second with one
+    row (row lane 0 alone), 1 250 is the largest count dl3_pwconv_partials returns (32 -> 172 at 40 000 rows: five trips, the
+    last one ragged in every unrolled slot).  The partial rows are integers, so their float64 fold is exact in any order and
+    the outputs are ONE fp32 rounding of the float64 expression; a row added twice or left out moves every sum by percent."""
+    rng = np.random.default_rng(996 + P)
+    C, count = 21, 40000.0
+    if P == 1250:
+        assert L.dl3_pwconv_partials(40000, 32, 172) == 1250
+    part = np.empty((P, C, 2), np.float32)
+    part[:, :, 0] = rng.integers(-9, 10, (P, C)) + np.arange(P)[:, None] % 7     # every row differs from its neighbours
+    part[:, :, 1] = rng.integers(40, 120, (P, C)) + np.arange(P)[:, None] % 5
+    gamma, beta = _pars(rng, C)
+    mm, mv = rng.normal(0, 1, C).astype(np.float32), rng.uniform(0.5, 2, C).astype(np.float32)
+    eps, mom = 1e-3, 0.99
+    unb = count / (count - 1) * count / (count - (1 + eps))
+    names = ("scale", "shift", "mean", "invstd", "mmean", "mvar")
+    bufs = [OO.guard_buffer(C, 1) for _ in names]
+    bufs[4][:C], bufs[5][:C] = mm, mv
+    d = [dev(b) for b in bufs]
+    call("dl3_bn_finalize", ptr(dev(part)), P, C, C, count, ptr(dev(gamma)), ptr(dev(beta)), eps, mom, unb, *[ptr(b) for b in d])
+    ref = OO.bn_finalize(part, P, C, 0, C, count, gamma, beta, eps, mom, unb, mm, mv)
+    assert (part[:, :, 1].astype(np.float64).sum(0) / count - ref["mean"] ** 2 > 0.01).all()   # (far from the variance clamp)
+    scale64 = ref["scale"]
+    mags = dict(scale=np.abs(scale64), shift=np.abs(beta.astype(np.float64)) + np.abs(ref["mean"] * scale64), mean=np.abs(ref["mean"]),
+                invstd=np.abs(ref["invstd"]), mmean=np.abs(ref["mmean"]), mvar=np.abs(ref["mvar"]))
+    for name, b in zip(names, d):
+        h = host(b)
+        OO.assert_guard(h, np.arange(C))
+        OO.assert_elementwise(h[:C], ref[name], mags[name], 1, "bn_finalize")
+    dpart = np.empty((P, C, 2), np.float32)
+    dpart[:, :, 0] = rng.integers(-9, 10, (P, C)) + np.arange(P)[:, None] % 7
+    dpart[:, :, 1] = rng.integers(-20, 21, (P, C)) + np.arange(P)[:, None] % 3
+    mean, invstd = rng.normal(0, 1, C).astype(np.float32), rng.uniform(0.5, 2, C).astype(np.float32)
+    for mode in (1, 0):
+        co = [dev(OO.guard_buffer(C, 1)) for _ in range(5)]
+        call("dl3_bn_bwd_finalize", ptr(dev(dpart)), P, C, C, count, ptr(dev(gamma)), ptr(dev(mean)), ptr(dev(invstd)), mode,
+             *[ptr(o) for o in co])
+        rb = OO.bn_bwd_finalize(dpart, P, C, 0, C, count, gamma, mean, invstd, mode)
+        mag = {k: np.abs(v) for k, v in rb.items()}
+        # cC = -a * s1 / n - b * mean: two terms that may cancel
+        mag["cC"] = np.abs(rb["cA"] * rb["dbeta"] / count) + np.abs(rb["cB"] * mean.astype(np.float64))
+        for name, o in zip(("cA", "cB", "cC", "dgamma", "dbeta"), co):
+            h = host(o)
+            OO.assert_guard(h, np.arange(C))
+            OO.assert_elementwise(h[:C], rb[name], mag[name], 1, "bn_bwd_finalize")
+        # the folded sums themselves are integers: exact
+        assert np.array_equal(host(co[3])[:C], dpart[:, :, 1].astype(np.float64).sum(0))
+        assert np.array_equal(host(co[4])[:C], dpart[:, :, 0].astype(np.float64).sum(0))
+
+
+@pytest.mark.parametrize("with_stats", [True, False], ids=["mean-invstd", "null-mean-invstd"])
+@pytest.mark.parametrize("C", [21, 257])
+def test_bn_frozen_centered(L, C, with_stats):
+    """dl3_bn_frozen_centered, the frozen BatchNorm whose producer subtracts the mean: scale = gamma / sqrt(var + eps) and invstd
+    at ONE fp32 rounding of the float64 value (the kernel evaluates them in double), shift = beta, neg_mean = -moving_mean and
+    mean = 0 bit for bit; C = 21 (one ragged workgroup) and 257 (a second workgroup with one channel); mean / invstd NULL"""
+    rng = np.random.default_rng(997 + C)
+    gamma, beta = _pars(rng, C)
+    mm = (rng.normal(0, 30, C)).astype(np.float32)        # |mean| >> sigma is what the centred form is for
+    mm[0] = 0.0                                           # (-0.0 is the negation of 0.0)
+    mv = rng.uniform(1e-4, 4, C).astype(np.float32)
+    eps = 1e-3
+    names = ("scale", "shift", "mean", "invstd", "neg_mean")
+    d = {n: dev(OO.guard_buffer(C, 1)) for n in names}
+    call("dl3_bn_frozen_centered", ptr(dev(gamma)), ptr(dev(beta)), ptr(dev(mm)), ptr(dev(mv)), eps, C, ptr(d["scale"]),
+         ptr(d["shift"]), ptr(d["mean"]) if with_stats else None, ptr(d["invstd"]) if with_stats else None, ptr(d["neg_mean"]))
+    inv64 = 1.0 / np.sqrt(mv.astype(np.float64) + float(np.float32(eps)))
+    h = {n: host(b) for n, b in d.items()}
+    for n in names:
+        OO.assert_guard(h[n], np.arange(C) if (with_stats or n not in ("mean", "invstd")) else np.arange(0))
+    OO.assert_elementwise(h["scale"][:C], gamma * inv64, np.abs(gamma * inv64), 1, "bn_frozen_centered")
+    assert np.array_equal(h["shift"][:C].view(np.uint32), beta.view(np.uint32))
+    assert np.array_equal(h["neg_mean"][:C].view(np.uint32), (-mm).view(np.uint32))
+    if with_stats:
+        OO.assert_elementwise(h["invstd"][:C], inv64, inv64, 1, "bn_frozen_centered")
+        assert np.array_equal(h["mean"][:C].view(np.uint32), np.zeros(C, np.uint32))

@@ -427,7 +427,7 @@ int dl3_softmax_xent_jaccard(const float *logits, const float *labels, const flo
 int dl3_upsample_softmax_xent_jaccard(const float *logits_lo, const float *labels, const float *weights, const float *nnz,
                                       const float *coef, float lambda, float *dlogits, float *loss_partial, int N, int Hi,
                                       int Wi, int Ho, int Wo, int C, void *stream);
-/* ---- focal loss in every form of the training loss tail (csrc/focal.hip; Lin et al. 2017 eq. 5 in softmax
+/* ---- focal loss in every form of the training loss tail (csrc/losstail.hip; Lin et al. 2017 eq. 5 in softmax
  * form, our own statement).  Inputs as the four loss kernels above take them (label outside 0..C-1: void; weights
  * nullable: w = 1, forced to 0 on void pixels; *nnz floored as there), plus
  *   alpha  device pointer to C floats >= 0, or NULL (every class 1); read once per workgroup into LDS

@@ -1,5 +1,5 @@
 // evaltail.hip — the evaluation tail: validation loss sums, metric counts, confusion matrix and (optionally) the argmax
-// mask from the LOW-resolution logits plus labels in one pass.  The evaluation twin of the training tails in misc.hip
+// mask from the LOW-resolution logits plus labels in one pass.  The evaluation twin of the training tails in losstail.hip
 // (dl3_upsample_softmax_xent_fold, dl3_shuffle_softmax_xent): the full-resolution logits / probabilities never exist.
 //   bilinear  logits_lo [N,Hi,Wi,C] -> TF1 legacy bilinear resize in registers (bit-identical to dl3_resize_bilinear_fwd)
 //   shuffle   u [N,H,W,C*r*r]       -> Subpixel._phase_shift by index (a pure permutation)

@@ -6,7 +6,7 @@
 //   dl3_jaccard_sums_{plain,bilinear}         per-workgroup partial rows [B][P][3][C] in double, a workgroup inside ONE image
 //   dl3_jaccard_coef                          folds them in a fixed order; kappa = present / (n_c n_legal), A = -kappa / U,
 //                                             Bc = kappa I / U^2, coef[B][C][2] = (A, Bc) rounded to float once; lambda * L_J
-//   dl3_{,upsample_}softmax_xent_jaccard      the cross-entropy tail of misc.hip, the same arithmetic, plus
+//   dl3_{,upsample_}softmax_xent_jaccard      the cross-entropy tail of losstail.hip, the same arithmetic, plus
 //                                             lambda u p_k (G_k - sum_c p_c G_c), G_c = A[c] at the label, else Bc[c]
 // No atomics: two runs are bit-identical.  Ordinary vector stores only.
 #include "tailmath.h"
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void jaccard_coef_kernel(const double *__restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// loss + gradient: xent32_kernel of misc.hip — thread = pixel, logits in registers, dlogits leave through an LDS
+// loss + gradient: the cross-entropy row_kernel of losstail.hip — thread = pixel, logits in registers, dlogits leave through an LDS
 // transpose — over grid = (P, B), so that a workgroup stays inside one image and stages that image's 2C coefficients
 // once.  The cross-entropy half repeats that kernel's arithmetic operation for operation (with an all-zero table the
 // gradient is its gradient bit for bit); loss_part carries the cross-entropy alone.

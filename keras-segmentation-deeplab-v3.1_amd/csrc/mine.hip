@@ -1,6 +1,6 @@
 // mine.hip — online hard-example mining in front of the training loss tails (DeepLab's top_k_percent_pixels /
 // hard_example_mining_step, restated from memory of deeplab/utils/train_utils.py): the step trains on the k largest
-// per-pixel losses only.  Three passes produce what the loss kernels of misc.hip already take as device pointers, mined
+// per-pixel losses only.  Three passes produce what the loss kernels of losstail.hip already take as device pointers, mined
 // sample weights w' and a mined normaliser n':
 //   dl3_pixel_xent_{plain,bilinear,shuffle}   v[m] = w[m] * -log clip(p_label, 1e-7, 1 - 1e-7), 0 for a void label, from
 //                                             the same three sources the training tails read

@@ -1,6 +1,6 @@
-// tailmath.h — the per-pixel arithmetic the output head's consumers share (device helpers only): misc.hip (resize and the
-// training loss tails), evaltail.hip (evaluation tail), crfunary.hip (CRF unary), mine.hip and jaccard.hip (the fronts of the
-// mined and the soft-Jaccard loss) and focal.hip (the focal loss tails) decode the same class scores.
+// tailmath.h — the per-pixel arithmetic the output head's consumers share (device helpers only): misc.hip (resize),
+// losstail.hip (the training loss tails, cross-entropy and focal), evaltail.hip (evaluation tail), crfunary.hip (CRF unary),
+// mine.hip and jaccard.hip (the fronts of the mined and the soft-Jaccard loss) decode the same class scores.
 #pragma once
 #include "common.h"
 

@@ -1,5 +1,5 @@
 """The case table of tests/test_gpu_head_classes.py: the six kernel families that decode the output head's class scores
-(csrc/misc.hip loss tails, focal.hip, jaccard.hip, mine.hip, evaltail.hip, crfunary.hip) at every class-count
+(csrc/losstail.hip, both of its pixel terms, jaccard.hip, mine.hip, evaltail.hip, crfunary.hip) at every class-count
 instantiation, and what a case needs on the host: its seeded inputs and the launch rules of those files restated in
 Python.  Importable without a GPU: tests/test_head_class_cases_host.py checks the table here against the sources, the
 references' own conditions and a deliberately wrong oracle.
@@ -49,7 +49,7 @@ def dispatch_maxc(C):
 
 
 def two_bucket_maxc(C):
-    """the fold and the training shuffle kernels pick by hand: <24> or <32>"""
+    """the fold and the training shuffle launchers (launch_fold, launch_shuffle) pick by hand: <24> or <32>"""
     return 24 if C <= 24 else 32
 
 
@@ -61,14 +61,14 @@ _T = ((24, ""), (32, ""))
 _F = ((24, "pref"), (24, "nopref"), (32, "pref"), (32, "nopref"))
 _V = tuple((m, v) for m in (8, 24, 32) for v in ("vec4", "scalar"))
 KERNELS = {
-    "dl3_softmax_xent": ("misc.hip", "xent32_kernel<false>", lambda C: 32, ((32, ""),)),
-    "dl3_upsample_softmax_xent": ("misc.hip", "xent32_kernel<true>", lambda C: 32, ((32, ""),)),
-    "dl3_upsample_softmax_xent_fold": ("misc.hip", "if (C <= 24) { if (pref) DL3_XENT(24, true)", two_bucket_maxc, _F),
-    "dl3_shuffle_softmax_xent": ("misc.hip", "shuffle_xent_kernel<24>", two_bucket_maxc, _T),
-    "dl3_focal_xent": ("focal.hip", "focal32_kernel<false>", lambda C: 32, ((32, ""),)),
-    "dl3_upsample_focal_xent": ("focal.hip", "focal32_kernel<true>", lambda C: 32, ((32, ""),)),
-    "dl3_upsample_focal_xent_fold": ("focal.hip", "if (C <= 24) { if (pref) DL3_FOCAL(24, true)", two_bucket_maxc, _F),
-    "dl3_shuffle_focal_xent": ("focal.hip", "shuffle_focal_kernel<24>", two_bucket_maxc, _T),
+    "dl3_softmax_xent": ("losstail.hip", "launch_rows<XentTerm, false>(", lambda C: 32, ((32, ""),)),
+    "dl3_upsample_softmax_xent": ("losstail.hip", "launch_rows<XentTerm, true>(", lambda C: 32, ((32, ""),)),
+    "dl3_upsample_softmax_xent_fold": ("losstail.hip", "launch_fold<XentTerm>(", two_bucket_maxc, _F),
+    "dl3_shuffle_softmax_xent": ("losstail.hip", "launch_shuffle<XentTerm>(", two_bucket_maxc, _T),
+    "dl3_focal_xent": ("losstail.hip", "launch_rows<FocalTerm, false>(", lambda C: 32, ((32, ""),)),
+    "dl3_upsample_focal_xent": ("losstail.hip", "launch_rows<FocalTerm, true>(", lambda C: 32, ((32, ""),)),
+    "dl3_upsample_focal_xent_fold": ("losstail.hip", "launch_fold<FocalTerm>(", two_bucket_maxc, _F),
+    "dl3_shuffle_focal_xent": ("losstail.hip", "launch_shuffle<FocalTerm>(", two_bucket_maxc, _T),
     "dl3_jaccard_sums_plain": ("jaccard.hip", "DL3_DISPATCH_MAXC(C, DL3_JSUMS)", dispatch_maxc, _D),
     "dl3_jaccard_sums_bilinear": ("jaccard.hip", "DL3_DISPATCH_MAXC(C, DL3_JSUMS)", dispatch_maxc, _D),
     "dl3_softmax_xent_jaccard": ("jaccard.hip", "xent32_jaccard_kernel<false>", lambda C: 32, ((32, ""),)),
@@ -86,8 +86,8 @@ KERNELS = {
 
 
 def fold_prefetches(Wi, Wo, C, pref_env):
-    """the launcher's condition of dl3_upsample_softmax_xent_fold and its focal twin (XENT_PS = kPS = 12, XENT_PP = kPP =
-    2; the test's device buffers are 16-byte aligned): pref_env is DL3_XENT_PREF, None when unset"""
+    """the condition of launch_fold, the launcher of dl3_upsample_softmax_xent_fold and its focal twin (kPrefFloats = 12,
+    kPrefPixels = 2; the test's device buffers are 16-byte aligned): pref_env is DL3_XENT_PREF, None when unset"""
     return (Wi * C <= 256 * 12 and Wo <= 256 * 2 and (Wi * C) % 4 == 0 and (Wo * C) % 4 == 0
             and not (pref_env is not None and int(pref_env) == 0))
 

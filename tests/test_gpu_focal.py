@@ -1,4 +1,4 @@
-"""The focal loss on the device (csrc/focal.hip): the four forms through the C ABI against the float64
+"""The focal loss on the device (csrc/losstail.hip): the four forms through the C ABI against the float64
 oracle under the project's yardstick (the fold form against today's fold kernel: both use __expf), the cross-entropy
 half bit for bit against today's loss kernels, the refusals, and the training step at model level — loss against the
 oracle on Engine.logits() under hipGraph replay, the plan, gamma = 0, evaluation untouched, a world of one, the device

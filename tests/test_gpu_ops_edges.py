@@ -1,5 +1,5 @@
 """-m gpu: the element-wise, BatchNorm-finaliser, resize, tap-gather, subsample, loss-tail and optimizer kernels of
-csrc/bn.hip and csrc/misc.hip on the paths the engine takes and tests/test_gpu_ops.py does not reach: padded leading
+csrc/bn.hip, csrc/misc.hip and csrc/losstail.hip on the paths the engine takes and tests/test_gpu_ops.py does not reach: padded leading
 dimensions, column slices, ragged row counts, misaligned pointers, capped grids that loop, ties and clamps.
 
 Every comparison is per element against the float64 restatement in tests/ops_oracle.py with one of its two derived
@@ -477,7 +477,7 @@ def _loss_chain(M, P, C):
 @pytest.mark.parametrize("variant", ["all", "no_weights", "no_probs", "no_dlogits"])
 @pytest.mark.parametrize("M,C", [(33007, 1), (33007, 2), (33007, 32), (33007, 33), (131072 + 77, 2)])
 def test_softmax_xent_kernel_switch_and_capped_partials(L, M, C, variant):
-    """dl3_softmax_xent: C = 32 is the last width of xent32_kernel, C = 33 the first of softmax_xent_kernel, C = 1 and 2
+    """dl3_softmax_xent: C = 32 is the last width of row_kernel, C = 33 the first of softmax_xent_kernel, C = 1 and 2
     the narrowest rows of the LDS transpose.  M = 33 007 > 32 768 caps dl3_rows_partials at P = 512 (515 without the
     cap; the last workgroup's tile is ragged: 33007 = 128 x 256 + 239); M = 131 149 > 512 x 256 = 131 072 makes the
     row loop of both kernels run a second time.  weights == NULL (every valid row weighs 1), probs == NULL with
@@ -561,7 +561,7 @@ def _upsample_case(rng, dims):
 
 
 def test_upsample_softmax_xent_capped_partials(L):
-    """xent32_kernel<UPSAMPLE> at (3, 3, 5, 110, 101, 4): M = 33 330 output pixels > 32 768: P = 512 (capped), the last
+    """row_kernel<XentTerm, UPSAMPLE> at (3, 3, 5, 110, 101, 4): M = 33 330 output pixels > 32 768: P = 512 (capped), the last
     workgroup's tile ragged (33330 = 130 x 256 + 50); a non-integer factor both ways"""
     dims = (3, 3, 5, 110, 101, 4)
     N, Hi, Wi, Ho, Wo, C = dims
@@ -590,7 +590,7 @@ def test_upsample_softmax_xent_capped_partials(L):
 
 @pytest.mark.parametrize("dims", [(70, 2, 2, 60, 4, 3), (3, 3, 5, 110, 101, 4)])
 def test_upsample_softmax_xent_fold_capped_rows(L, dims):
-    """xent32_fold_kernel: one workgroup per output row behind dl3_xent_fold_partials' cap of 4096.  (70, 2, 2, 60, 4,
+    """fold_kernel<XentTerm, ..>: one workgroup per output row behind dl3_xent_fold_partials' cap of 4096.  (70, 2, 2, 60, 4,
     3): N*Ho = 4200 rows > 4096: rows 4096..4199 are second trips of workgroups 0..103.  (3, 3, 5, 110, 101, 4): 330
     rows, one each.  The first takes the form without prefetch (Wi*C = 6 is no multiple of 4), the second the
     prefetching one (Wi*C = 20, Wo*C = 404: whole float4s; 101 pixels: one per thread, the second slot idle)."""

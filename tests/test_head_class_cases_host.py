@@ -51,19 +51,33 @@ def test_the_restated_launch_rules_are_the_sources():
         assert 'extern "C" int %s(' % entry in src, entry
         assert text in src, (entry, text)
     # the kernels with one register row for every C take it from kHeadMaxC
-    for fname, n in (("misc.hip", 1), ("focal.hip", 1), ("jaccard.hip", 1)):
+    for fname, n in (("losstail.hip", 1), ("jaccard.hip", 1), ("misc.hip", 0)):
         assert _src(fname).count("constexpr int MAXC = kHeadMaxC;") == n, fname
-    # the fold launchers' prefetch condition, as fold_prefetches restates it
-    assert "#define XENT_PS 12" in _src("misc.hip") and "#define XENT_PP 2" in _src("misc.hip")
-    assert "constexpr int kPS = 12;" in _src("focal.hip") and "constexpr int kPP = 2;" in _src("focal.hip")
-    for fname, ps, pp in (("misc.hip", "XENT_PS", "XENT_PP"), ("focal.hip", "kPS", "kPP")):
-        assert ("(long)Wi * C <= 256L * %s && Wo <= 256 * %s && (Wi * C) %% 4 == 0 && ((long)Wo * C) %% 4 == 0" % (ps, pp)
-                in _src(fname)), fname
+    # a form of the training loss tail has one kernel body and one launcher, whatever the pixel term: the duplicate that
+    # the focal loss once was (csrc/focal.hip, a copy of every kernel) does not come back
+    tail = _src("losstail.hip")
+    assert not os.path.exists(os.path.join(CSRC, "focal.hip"))
+    for body in ("row_kernel", "fold_kernel", "shuffle_kernel"):
+        assert len(re.findall(r"__global__[^;{]*\bvoid %s\(" % body, tail)) == 1, body
+        assert len(re.findall(r"^template <class Term, [^>]*class\.\.\. TermArgs>\n__global__[^;{]*\bvoid %s\(" % body, tail,
+                              re.M)) == 1, body
+    # the two-bucket choices of the fold and the shuffle launcher, as two_bucket_maxc restates them
+    assert tail.count("if (C <= 24) { if (pref) DL3_FOLD(24, true); else DL3_FOLD(24, false); }") == 1
+    assert tail.count("else { if (pref) DL3_FOLD(32, true); else DL3_FOLD(32, false); }") == 1
+    assert tail.count("if (C <= 24) DL3_SHUFFLE(24); else DL3_SHUFFLE(32);") == 1
+    assert "(fold_kernel<Term, MAXC_, PREF_, TermArgs...>)" in tail and "(shuffle_kernel<Term, MAXC_, TermArgs...>)" in tail
+    assert "(row_kernel<Term, UPSAMPLE, TermArgs...>)" in tail
+    # the fold launcher's prefetch condition, as fold_prefetches restates it
+    assert tail.count("constexpr int kPrefFloats = 12, kPrefPixels = 2;") == 1
+    assert re.sub(r"\s+", " ", tail).count(
+        "const bool pref = (long)Wi * C <= 256L * kPrefFloats && Wo <= 256 * kPrefPixels && (Wi * C) % 4 == 0 && "
+        "((long)Wo * C) % 4 == 0 && aligned16(logits_lo) && !(pe && atoi(pe) == 0);") == 1
+    assert tail.count('getenv("DL3_XENT_PREF")') == 1
     assert "const bool vec = (Wo % 4 == 0) && aligned16(labels)" in _src("evaltail.hip")
     # the tile rules
     assert "int pb = (int)((48u << 10) / ((size_t)C * (r * r + 1) * sizeof(float)));" in _src("tailmath.h")
     assert "subpixel_tile_pixels(W, C, r, (1024 + r * r - 1) / (r * r))" in _src("tailmath.h")
-    assert "subpixel_tile_pixels(W, C, r, 8)" in _src("misc.hip") and "subpixel_tile_pixels(W, C, r, 8)" in _src("focal.hip")
+    assert tail.count("const int PB = subpixel_tile_pixels(W, C, r, 8);") == 2   # the launcher, and the partials it sizes
 
 
 def test_the_table_reaches_every_kernel_the_sources_define():

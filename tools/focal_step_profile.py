@@ -1,4 +1,4 @@
-"""Cost of the focal loss (csrc/focal.hip).
+"""Cost of the focal loss (csrc/losstail.hip).
 
   python tools/focal_step_profile.py step [--batch 16] [--size 512] [--steps 30] [--warmup 5] [--gamma 2.0] [--plain-only]
       the training step (the captured fwd_bwd plan + Adam) of MobileNetV2 at size x size x 21 on a resident batch, one

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Every entry point of the output head's six files (csrc/misc.hip, evaltail.hip, crfunary.hip, mine.hip, jaccard.hip,
-focal.hip) through capi on fixed seeded inputs — the A/B aid of a refactor of csrc/tailmath.h.  DL3_LIBPATH selects the library.
+"""Every entry point of the output head's six files (csrc/misc.hip, losstail.hip, evaltail.hip, crfunary.hip, mine.hip,
+jaccard.hip) through capi on fixed seeded inputs — the A/B aid of a refactor of csrc/tailmath.h.  DL3_LIBPATH selects the library.
 
     head_entry_points.py --dump DIR          small shapes (the operator tests'), every output to DIR/<case>.<name>.npy
     head_entry_points.py --compare DIR DIR   byte comparison of two dumps; prints what differs (CPU only)

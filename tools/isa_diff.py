@@ -3,6 +3,7 @@
 
     tools/isa_diff.py [--rev REV] [TREE_A [TREE_B]] [-o profiles/head_refactor_isa.txt]
     tools/isa_diff.py --files-a pwgemm.hip --files-b pwgemm.hip pwstream.hip pwlds.hip ... [-o profiles/pwgemm_split_isa.txt]
+    tools/isa_diff.py --files-a misc.hip focal.hip --files-b misc.hip losstail.hip --rename 'xent32_kernel<false>=row_kernel<XentTerm, false, float*>' ...
 
 Without trees, A is a temporary `git worktree` of REV (default HEAD: the parent of uncommitted work; pass HEAD~1 once
 the work is committed) and B is the working tree.  Each file is cross-compiled to gfx950 device assembly with the flags
@@ -15,7 +16,8 @@ Without --files-a / --files-b the output head's six files are compared file by f
 that a tree does not have yet holds no kernels there).  With them (either one defaults to
 the other) the kernels of all files of a side are pooled — code that moved between files — and paired by demangled name,
 template arguments kept, `(anonymous namespace)::` and the namespace of the GEMM argument structs (`pw::`) stripped; a
-kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison.
+kernel's own mangled symbol inside its stream is replaced by a placeholder before the comparison.  --rename OLD=NEW
+(repeatable) pairs a kernel of A named OLD with the kernel of B named NEW: code whose name changed on the way.
 
 --memseq NAME adds, below the table, for every kernel named *NAME* that both sides have: whether the sequence of
 global_load_* / global_store_* instructions and vmcnt(N) waits in front of the kernel's first LDS or barrier instruction
@@ -30,7 +32,7 @@ import subprocess
 import sys
 import tempfile
 
-FILES = ["misc.hip", "evaltail.hip", "crfunary.hip", "mine.hip", "jaccard.hip", "focal.hip"]
+FILES = ["misc.hip", "losstail.hip", "evaltail.hip", "crfunary.hip", "mine.hip", "jaccard.hip"]
 CSRC = os.path.join("keras-segmentation-deeplab-v3.1_amd", "csrc")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VOLATILE = re.compile(r"^\s*\.(file|ident)\b|__hip_cuid_")
@@ -97,11 +99,11 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def pool(asm, side, files):
+def pool(asm, side, files, renames={}):
     """{pairing name: (file, stream, stats)} over all files of one side"""
     out = {}
     for f in files:
-        pretty = demangle(list(asm[(side, f)]))
+        pretty = {n: renames.get(p, p) for n, p in demangle(list(asm[(side, f)])).items()}
         for n, v in asm[(side, f)].items():
             if pretty[n] in out:
                 sys.exit("%s: two kernels named %s (%s, %s)" % (side, pretty[n], out[pretty[n]][0], f))
@@ -115,6 +117,8 @@ def main():
     ap.add_argument("--rev", default="HEAD")
     ap.add_argument("--files-a", nargs="+", metavar="FILE", help="csrc/ files of tree A, pooled (default: those of --files-b)")
     ap.add_argument("--files-b", nargs="+", metavar="FILE", help="csrc/ files of tree B, pooled (default: those of --files-a)")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="with --files-a / --files-b: kernel OLD of A is paired with (and shown as) kernel NEW of B")
     ap.add_argument("-o", "--output", default=None)
     ap.add_argument("--diff", default=None, metavar="NAME", help="also print the unified diff of the kernels named *NAME*")
     ap.add_argument("--memseq", default=None, metavar="NAME",
@@ -144,7 +148,7 @@ def main():
     n_a = n_b = 0
     diffs, both = [], []
     for fa, fb in groups:
-        ka, kb = pool(asm, "a", fa), pool(asm, "b", fb)
+        ka, kb = pool(asm, "a", fa, dict(r.split("=", 1) for r in a.rename)), pool(asm, "b", fb)
         n_a, n_b = n_a + len(ka), n_b + len(kb)
         for n in list(ka) + [n for n in kb if n not in ka]:
             sa, sb = ka.get(n), kb.get(n)
@@ -160,7 +164,8 @@ def main():
     head = "%-12s %-44s %-9s | %6s %5s %7s %6s | %6s %5s %7s %6s" % (
         "file", "kernel", "stream", "A:inst", "vgpr", "scratch", "lds", "B:inst", "vgpr", "scratch", "lds")
     text = "\n".join(["# A = %s, B = %s; gfx950" % (a.trees[0] if a.trees else a.rev,
-                                                    a.trees[1] if len(a.trees) > 1 else "the working tree"), head] + rows +
+                                                    a.trees[1] if len(a.trees) > 1 else "the working tree")] +
+                     ["# A's %s is B's %s" % tuple(r.split("=", 1)) for r in a.rename] + [head] + rows +
                      ["# %d kernels: %d identical, %d not; A has %d, B has %d" % (len(rows), n_same, n_diff, n_a, n_b)]) + "\n"
     for n, sa, sb in both:
         if a.memseq and a.memseq in n:
